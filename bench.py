@@ -18,16 +18,24 @@ Multi-GPU (frames mode = C4, weak scaling; rowtile mode = C5, strong scaling):
     (sv_multi_gpu_dev when gathering).
 value = frames of all GPUs / max wall time of the timed region.
 
+A plain run sets up, warms up, times --steps steps and prints the line: `value`,
+`ms_per_step` and the figures the timed region's own HIP events give (`roofline` launch
+times, `distributed`).  --dump-outputs DIR also writes what the last timed step computed
+(DIR/<name>.npy, float32; the inputs are seeded, so two builds compare output for output).
+Everything else takes runs of its own and is measured only with --full.
+
 Extra JSON fields:
   roofline      k_match against the HBM roofline with SURVEY.md §8(d)'s algorithmic bytes
                 (6 B/px: 2 u8 images read + the f32 disparity map); launch times from HIP
-                events inside the timed region; `traffic` and `valu` from rocprofv3 PMC passes
-                run live by this script on this box (separate --pmc passes, a child process
+                events inside the timed region; --full: `traffic` and `valu` from rocprofv3
+                PMC passes run live by this script (separate --pmc passes, a child process
                 each; --no-live-pmc skips them)
-  host_path     the drop-in create_depth_map (BGR NumPy in -> NumPy out, one frame per call,
-                PCIe-inclusive) and its pipelined form (several frames in flight)
-  cpu_baseline  the C oracle (oracle/sv_oracle.c, OpenMP over every core of this process's
-                affinity) on full frames
+  verified      --full: the last timed step's maps against the C oracle, bit-exact
+  aux_kernels   --full: HBM rooflines of the memory-bound kernels around k_match
+  host_path     --full: the drop-in create_depth_map (BGR NumPy in -> NumPy out, one frame per
+                call, PCIe-inclusive) and its pipelined form (several frames in flight)
+  cpu_baseline  --full: the C oracle (oracle/sv_oracle.c, OpenMP over every core of this
+                process's affinity) on full frames
 """
 from __future__ import annotations
 
@@ -568,6 +576,37 @@ def map_to_disp(eng, d_map, index, n_px, H, W, u8):
     return eng.to_host(d_map + 2 * n_px * index, (H, W), np.int16).astype(np.float32) / np.float32(16.0)
 
 
+DUMP_BUDGET_BYTES = 60 << 20   # --dump-outputs: all files together stay under 64 MB
+DUMP_SAMPLE_SEED = 20240
+
+
+def dump_outputs(path, arrays, writers=1):
+    """--dump-outputs: every array of `arrays` (name -> host array) as path/<name>.npy in
+    float32 (exact for the path's f32 / int16 / u8 maps).  The arrays share one element budget
+    (split over `writers` processes that dump into the same directory, one per rank); one
+    larger than its share is written as a fixed sample: the elements at sorted flat indices
+    drawn without replacement by default_rng(DUMP_SAMPLE_SEED), which depend only on the
+    array's size, so two runs with the same arguments sample the same pixels."""
+    os.makedirs(path, exist_ok=True)
+    if not arrays:
+        return {}
+    share = DUMP_BUDGET_BYTES // 4 // max(1, writers) // len(arrays)
+    picks, written = {}, {}
+    for name, a in arrays.items():
+        flat = np.ascontiguousarray(a).reshape(-1)
+        if flat.size > share:
+            if flat.size not in picks:
+                rng = np.random.default_rng(DUMP_SAMPLE_SEED)
+                picks[flat.size] = np.sort(rng.choice(flat.size, size=share, replace=False))
+            out = flat[picks[flat.size]].astype(np.float32)
+            written[name] = {"shape": list(a.shape), "sampled": int(out.size)}
+        else:
+            out = np.asarray(a, dtype=np.float32)
+            written[name] = {"shape": list(a.shape), "sampled": None}
+        np.save(os.path.join(path, name + ".npy"), out)
+    return written
+
+
 def init_comms(devices, required: bool):
     """One process, N devices: an RCCL group (ncclCommInitAll) -> (comms, "").  When it
     cannot start: (None, reason) — the caller gathers with hipMemcpyPeerAsync
@@ -661,6 +700,16 @@ def parse_args(argv=None):
                          "is 1,890 waves per frame, 26 frames = 49,140 waves = 24.0 rounds of the "
                          "2,048 wave slots (16 frames = 14.8 rounds, a last round 77%% full): +0.9%% "
                          "frames/s, C3 (win 11) +1.1%% (profiles/r05ag, r05ai)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need, each in a run of its "
+                         "own after the timed steps: the bit-exact check of the last step's maps "
+                         "against the C oracle, the rocprofv3 trace / PMC passes of the roofline, "
+                         "the aux-kernel rooflines, the host path and the CPU baseline (the "
+                         "--no-* options below then skip single ones)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write the arrays the last timed step computed as "
+                         "DIR/<name>.npy (float32; at most 64 MB in all: a larger array as a fixed, "
+                         "seeded sample of its elements)")
     ap.add_argument("--cpu-seconds", type=float, default=10.0)
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-profile", action="store_true", help="no HIP events in the timed loop")
@@ -1165,13 +1214,66 @@ def main():
     if args.pmc_child:
         print(json.dumps({"pmc_child": True, "value": value}), flush=True)
         return
+    last = args.steps - 1 if args.steps > 0 else max(0, n_warm - 1)
+
+    def last_outputs():
+        """name -> host array of what step `last` left for the caller of the timed path: the
+        (depth f32, disparity f32, depth u8) stacks of its frames on every GPU of this process,
+        or the maps gathered on GPU 0 / rank 0 (u8 indices or int16 x16 as the run gathers
+        them; with --root-outputs full the three expanded outputs)."""
+        sfx = f"_rank{rank}" if launched else ""
+        outs = {}
+
+        def three(e, name, d_depth, d_disp, d_norm, n):
+            outs["depth" + name] = e.to_host(d_depth, (n, H, W), np.float32)
+            outs["disparity" + name] = e.to_host(d_disp, (n, H, W), np.float32)
+            outs["depth_u8" + name] = e.to_host(d_norm, (n, H, W), np.uint8)
+
+        def gmap(name, d_map, n):
+            outs[name] = eng.to_host(d_map, (n, H, W), np.uint8 if gather_u8 else np.int16)
+        if rowtile and launched:
+            if rank == 0:
+                tl = tiles[rt["last"]]
+                if root_full or world == 1:
+                    three(eng, sfx, tl.out_a, tl.disp, tl.out_u8, 1)
+                else:
+                    gmap("gathered_map" + sfx, tl.m16, 1)
+        elif rowtile:
+            if root_full or not glanes:
+                three(eng, "", *(glanes[rt["last"]][2:5] if glanes else (depth[0], disp[0], norm[0])), 1)
+            else:
+                gmap("gathered_map", glanes[rt["last"]][5], 1)
+        elif gather_all:
+            _, _, ldep, ldis, lnor, lmap = glanes[last % 2]
+            if root_full:
+                three(eng, "", ldep, ldis, lnor, out_frames)
+            else:
+                gmap("gathered_map", lmap, out_frames)
+        else:
+            engs, depth_o, disp_o, norm_o = lanes[last % nstreams]
+            if gathered is not None:
+                gs = last % 2
+                depth_o, disp_o, norm_o = [gset[gs][0]], [gset[gs][1]], [gset[gs][2]]
+            for k, e in enumerate(engs):
+                name = sfx + (f"_gpu{k}" if len(engs) > 1 else "")
+                three(e, name, depth_o[k], disp_o[k], norm_o[k], B)
+                if harris:
+                    outs["harris" + name] = e.to_host(hmaps_l[last % nstreams][k], (B, H, W), np.float32)
+            if gathered is not None and rank == 0:
+                gmap("gathered_map" + sfx, gathered[last % 2], world * B)
+                if expanded is not None:
+                    three(eng, "_expanded" + sfx, *expanded[last % 2], (world - 1) * B)
+        return outs
+
+    dumped = None
+    if args.dump_outputs:
+        dumped = dump_outputs(args.dump_outputs, last_outputs(), writers=world)
 
     # ---- the timed steps' own outputs, checked bit-exactly (outside the timed region) ----
     verified, verify_info = None, None
-    if not args.no_verify and args.cost != "sgbm":
+    if args.full and not args.no_verify and args.cost != "sgbm":
         t_v = time.perf_counter()
         ver = Verifier(D, win, args.cost, host_cores()[0])
-        last = args.steps - 1 if args.steps > 0 else max(0, n_warm - 1)
         f0 = (last * B) % F
         zs = sorted({0, B - 1})
         if rowtile:
@@ -1250,7 +1352,7 @@ def main():
                                   + (" + Harris within 1e-4" if harris else ""),
                        "when": "after the timed region: maps of the LAST timed step",
                        "seconds": round(time.perf_counter() - t_v, 2)}
-    elif args.cost == "sgbm":
+    elif args.full and args.cost == "sgbm":
         verify_info = {"skipped": "SGBM mode: the NumPy SGBM-3WAY oracle takes ~15 s per 1080p "
                                   "frame; tests/test_sgbm.py checks the kernels bit-exactly"}
     # the collectives are over: from here on every phase (rocprofv3 passes, host path, CPU
@@ -1276,7 +1378,8 @@ def main():
     roofline = None
     pmc = {}
     if k_avg_s:
-        if rank == 0 and not args.no_live_pmc and not launched and len(engines) == 1 and not rowtile:
+        if (rank == 0 and args.full and not args.no_live_pmc and not launched and len(engines) == 1
+                and not rowtile):
             t_p = time.perf_counter()
             pmc = live_pmc(args, ("sgbm",) if args.cost == "sgbm" else
                            ("k_ssd_mfma", "k_match") if args.cost == "ssd" else ("k_match",))
@@ -1448,8 +1551,10 @@ def main():
                    "schedule": "split (match stream + median stream)" if split else
                                (f"lanes ({nstreams} contexts alternating steps)" if nstreams > 1 else "one stream"),
                    "parallelism": parallelism},
+        "full": bool(args.full),
         "verified": verified,
         "verify": verify_info,
+        "dumped_outputs": dumped,
         "distributed": dist,
         "hbm_gbs_frame_path": round(frame_bytes * value / 1e9, 2),
         # BASELINE.md's fixed roofline formulas, per GPU: 6*H*W algorithmic bytes and
@@ -1469,7 +1574,7 @@ def main():
         result["aux_kernels"] = {
             "k_remap_bgr2gray": hbm_entry("k_remap<3,gray>", 10 * n_px * B, remap_ms, remap_n)}
         rect.close()
-    elif solo and not rowtile and not args.no_aux:
+    elif solo and args.full and not rowtile and not args.no_aux:
         try:
             result["aux_kernels"] = aux_kernels(eng, H, W, B, med_ms, med_n, blocker=lambda: step(0),
                                                 frames=(dL[0], dR[0]), maps=disp[0])
@@ -1486,12 +1591,12 @@ def main():
         result["aux_kernels"]["k_harris"] = {
             "fused": "Harris blocks inside the k_median_i16 launch (sv_depth_map_batch_dev, out.harris): "
                      "median_post_avg_us includes them"}
-    if solo and not args.no_host_path and args.cost != "sgbm" and not rectify:
+    if solo and args.full and not args.no_host_path and args.cost != "sgbm" and not rectify:
         try:
             result["host_path"] = host_path(H, W, D, win)
         except Exception as e:  # reported, never required
             log(f"host path failed: {e}")
-    if solo and not args.no_cpu_baseline:
+    if solo and args.full and not args.no_cpu_baseline:
         try:
             result["cpu_baseline"] = cpu_baseline(H, W, D, win, args.cost, args.cpu_seconds,
                                                   harris=harris)

@@ -36,6 +36,42 @@ def test_gather_is_the_default_for_multi_gpu_frames():
     assert not bench.parse_args([]).no_verify
 
 
+def test_full_is_off_by_default_and_keeps_every_extra_on():
+    """A plain run measures the headline figure only; --full turns the oracle check, the PMC
+    passes, the aux kernels, the host path and the CPU baseline on, each with its --no-* switch."""
+    a = bench.parse_args(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert not a.full and a.dump_outputs is None and (a.steps, a.warmup) == (7, 2)
+    a = bench.parse_args(["--full", "--dump-outputs", "d"])
+    assert a.full and a.dump_outputs == "d"
+    assert not (a.no_verify or a.no_live_pmc or a.no_aux or a.no_host_path or a.no_cpu_baseline)
+    assert bench.parse_args(["--full", "--no-aux"]).no_aux
+
+
+def test_dump_outputs_writes_float32_and_samples_large_arrays(tmp_path, monkeypatch):
+    """Small arrays are written whole; an array over its share of the budget is a fixed sample
+    (sorted flat indices from a seeded generator that depend on the size only): the same
+    pixels on every run, values taken from the array, all files together under the budget."""
+    assert bench.DUMP_BUDGET_BYTES <= 64 * 10 ** 6
+    monkeypatch.setattr(bench, "DUMP_BUDGET_BYTES", 4 * 3 * 1000)   # 1000 elements per array
+    rng = np.random.default_rng(3)
+    small = rng.integers(0, 256, (2, 10, 40), dtype=np.uint8)
+    big = rng.random((3, 50, 70), dtype=np.float32)
+    big16 = (big * 4000).astype(np.int16)
+    info = bench.dump_outputs(str(tmp_path / "a"), {"small": small, "big": big, "big16": big16})
+    assert info == {"small": {"shape": [2, 10, 40], "sampled": None},
+                    "big": {"shape": [3, 50, 70], "sampled": 1000},
+                    "big16": {"shape": [3, 50, 70], "sampled": 1000}}
+    got = {n: np.load(str(tmp_path / "a" / (n + ".npy"))) for n in info}
+    assert all(a.dtype == np.float32 for a in got.values())
+    assert sum(a.nbytes for a in got.values()) <= 4 * 3 * 1000
+    np.testing.assert_array_equal(got["small"], small.astype(np.float32))
+    idx = np.sort(np.random.default_rng(bench.DUMP_SAMPLE_SEED).choice(big.size, 1000, replace=False))
+    np.testing.assert_array_equal(got["big"], big.reshape(-1)[idx])
+    np.testing.assert_array_equal(got["big16"], big16.reshape(-1)[idx].astype(np.float32))
+    bench.dump_outputs(str(tmp_path / "b"), {"small": small, "big": big.copy(), "big16": big16})
+    np.testing.assert_array_equal(np.load(str(tmp_path / "b" / "big.npy")), got["big"])   # same pixels
+
+
 def test_default_batch_and_lanes_at_1080p():
     """One GPU at 1920x1080: 8-frame steps over 2 stream lanes (16 resident frames, one 8-frame
     set per lane); N > 1 (gather beside the compute): 26-frame steps on one

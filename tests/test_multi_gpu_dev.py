@@ -676,7 +676,7 @@ def test_bench_under_torch_distributed_run_two_ranks(mode, root_outputs, fmt, ba
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", str(_port()), "bench.py", "--gpus", "2",
            "--steps", "3", "--warmup", "1", "--height", "96", "--width", "400", "--num-disp", "64",
-           "--frames", "2", "--batch", "2", "--mode", mode, "--no-live-pmc", "--no-aux",
+           "--frames", "2", "--batch", "2", "--mode", mode, "--full", "--no-live-pmc", "--no-aux",
            "--no-host-path", "--no-cpu-baseline", "--hang-timeout", "90", "--root-outputs", root_outputs,
            "--gather-format", fmt, "--band-inputs", bands]
     r = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=150)
@@ -731,7 +731,7 @@ def test_bench_one_process_rehearsal(ngpu, mode, root_outputs, fmt, bands):
            "--warmup", "1", "--height", str(H), "--width", str(W), "--num-disp", "64",
            "--frames", "4", "--batch", str(B), "--mode", mode, "--root-outputs", root_outputs,
            "--gather-format", fmt, "--band-inputs", bands,
-           "--no-live-pmc", "--no-aux", "--no-host-path", "--no-cpu-baseline", "--hang-timeout", "90"]
+           "--full", "--no-live-pmc", "--no-aux", "--no-host-path", "--no-cpu-baseline", "--hang-timeout", "90"]
     r = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=150)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     import json
@@ -760,7 +760,7 @@ def test_bench_rccl_init_failure_falls_back_to_peer_copies():
     import json
     cmd = [sys.executable, "bench.py", "--gpus", "3", "--rehearse", "--steps", "3", "--warmup", "1",
            "--height", "96", "--width", "400", "--num-disp", "64", "--frames", "2", "--batch", "2",
-           "--no-live-pmc", "--no-aux", "--no-host-path", "--no-cpu-baseline", "--hang-timeout", "90"]
+           "--full", "--no-live-pmc", "--no-aux", "--no-host-path", "--no-cpu-baseline", "--hang-timeout", "90"]
     env = dict(os.environ, SV_RCCL_INIT_FAIL="1")
     r = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=150, env=env)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
@@ -776,7 +776,7 @@ def test_bench_rccl_init_failure_falls_back_to_peer_copies():
 
 def test_bench_single_gpu_verifies_its_timed_outputs():
     cmd = [sys.executable, "bench.py", "--steps", "3", "--warmup", "1", "--height", "120",
-           "--width", "400", "--num-disp", "64", "--frames", "4", "--batch", "2", "--no-live-pmc",
+           "--width", "400", "--num-disp", "64", "--frames", "4", "--batch", "2", "--full", "--no-live-pmc",
            "--no-aux", "--no-host-path", "--no-cpu-baseline", "--harris"]
     r = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
@@ -784,6 +784,38 @@ def test_bench_single_gpu_verifies_its_timed_outputs():
     res = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
     assert res["verified"] is True and res["distributed"] is None
     assert len(res["verify"]["checked"]) == 4     # frames 0 and B-1: maps + Harris each
+
+
+def test_bench_plain_run_dumps_its_last_step(tmp_path):
+    """A plain run (no --full) times its steps and nothing else: no check against the oracle, no
+    aux kernels, host path or CPU baseline.  --dump-outputs writes the last timed step's three
+    maps as float32 .npy files; the inputs are seeded (step 2 of 3, batch 2 of 4 frames: seeds
+    0 and 1), so the dumped maps equal the C oracle's bit for bit."""
+    import json
+    H, W, D, win, B = 120, 400, 64, 9, 2
+    out = str(tmp_path / "maps")
+    cmd = [sys.executable, "bench.py", "--gpus", "1", "--steps", "3", "--warmup", "1",
+           "--warmup-seconds", "0", "--height", str(H), "--width", str(W), "--num-disp", str(D),
+           "--win", str(win), "--frames", "4", "--batch", str(B), "--streams", "1",
+           "--dump-outputs", out]
+    r = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
+    res = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
+    assert res["steps"] == 3 and res["ms_per_step"] > 0 and res["value"] > 0
+    assert abs(res["value"] - 3 * B / (3 * res["ms_per_step"] * 1e-3)) <= 0.01 * res["value"]
+    assert res["full"] is False and res["verified"] is None and res["verify"] is None
+    assert res["aux_kernels"] is None and res["host_path"] is None and res["cpu_baseline"] is None
+    assert sorted(os.listdir(out)) == ["depth.npy", "depth_u8.npy", "disparity.npy"]
+    got = {n: np.load(os.path.join(out, n + ".npy")) for n in ("depth", "disparity", "depth_u8")}
+    for n, a in got.items():
+        assert a.dtype == np.float32 and a.shape == (B, H, W), (n, a.dtype, a.shape)
+        assert res["dumped_outputs"][n] == {"shape": [B, H, W], "sampled": None}
+    for z in range(B):     # last step i = 2: frames (2 * B) % 4 = 0 .. B-1 of seed 0
+        L, R, _ = stereo_pair(H, W, D, seed=z)
+        e_disp, e_depth, e_norm = _oracle(L, R, D, win)
+        np.testing.assert_array_equal(got["disparity"][z], e_disp)
+        np.testing.assert_array_equal(got["depth"][z], e_depth)
+        np.testing.assert_array_equal(got["depth_u8"][z], e_norm.astype(np.float32))
 
 
 # ---- cross-stream ordering of the context scratch (ADVICE r01) -----------------------------------

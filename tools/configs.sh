@@ -1,14 +1,17 @@
 #!/bin/bash
 # Bench lines for every BASELINE.json config on one GPU (C4/C5's multi-GPU runs are the
-# driver's); each run under its own time limit, stop on a hard failure.
-cd "${GRAFT_REPO_ROOT:-/root/repo}" || exit 2
-mkdir -p gpurun_out
+# driver's); each run under its own time limit, stop on a hard failure.  --full: every run
+# checks its timed outputs against the oracle (a mismatch ends the sweep) and reports the aux
+# kernels.  Logs go to $OUT (default: bench_out/ under the repository root).
+cd "$(dirname "$0")/.." || exit 2
+OUT=${OUT:-bench_out}
+mkdir -p "$OUT"
 run() {
   local name=$1; shift
-  timeout -k 10 300 python bench.py --no-cpu-baseline --no-live-pmc --no-host-path "$@" > gpurun_out/cfg_$name.log 2>&1
+  timeout -k 10 300 python bench.py --full --no-cpu-baseline --no-live-pmc --no-host-path "$@" > "$OUT/cfg_$name.log" 2>&1
   local rc=$?
-  if [ $rc -ne 0 ]; then echo "$name rc=$rc"; tail -n 5 gpurun_out/cfg_$name.log; exit $rc; fi
-  python3 - "$name" gpurun_out/cfg_$name.log <<'PY'
+  if [ $rc -ne 0 ]; then echo "$name rc=$rc"; tail -n 5 "$OUT/cfg_$name.log"; exit $rc; fi
+  python3 - "$name" "$OUT/cfg_$name.log" <<'PY'
 import json, sys
 for line in open(sys.argv[2]):
     if line.startswith("{"):
@@ -29,5 +32,5 @@ run ssd_1080p_d128_w11 --cost ssd --win 11
 run ssd_1080p_d128_w15 --cost ssd --win 15
 run sgbm_1080p_d320_w7 --cost sgbm --num-disp 320 --win 7 --batch 1 --steps 40
 run sgbm_1080p_d320_w7_3calls --cost sgbm --num-disp 320 --win 7 --batch 1 --streams 3 --steps 40
-timeout -k 10 300 python tools/host_rate.py > gpurun_out/host_rate.log 2>&1; tail -n 1 gpurun_out/host_rate.log
-timeout -k 10 300 python tools/host_rate.py 480 640 64 9 >> gpurun_out/host_rate.log 2>&1; tail -n 1 gpurun_out/host_rate.log
+timeout -k 10 300 python tools/host_rate.py > "$OUT/host_rate.log" 2>&1; tail -n 1 "$OUT/host_rate.log"
+timeout -k 10 300 python tools/host_rate.py 480 640 64 9 >> "$OUT/host_rate.log" 2>&1; tail -n 1 "$OUT/host_rate.log"

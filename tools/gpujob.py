@@ -10,7 +10,8 @@ abort, a time limit or a failing test ends the call: nothing more touches the GP
 
     tests[=PYTEST_ARGS]        pytest -m gpu (default: the whole GPU suite)
     smoke                      __graft_entry__.smoke()
-    bench[=ARGS]               python bench.py ARGS            (summary line printed)
+    bench[=ARGS]               python bench.py ARGS            (summary line printed; --full among
+                               ARGS adds the oracle check, rooflines, host path, CPU baseline)
     trace[=ARGS]               rocprofv3 --kernel-trace --stats over bench.py ARGS
     pmc=C1,C2,..[@ARGS]        one rocprofv3 --pmc pass over bench.py ARGS (counters summed
                                per kernel, mean per dispatch printed)
@@ -35,7 +36,8 @@ import sys
 import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-BENCH_QUIET = ["--no-cpu-baseline", "--no-live-pmc", "--no-host-path"]
+# --full keeps the bit-exact check of the timed outputs (and, outside a trace, the aux kernels)
+BENCH_QUIET = ["--full", "--no-cpu-baseline", "--no-live-pmc", "--no-host-path"]
 LIMITS = {"tests": 900, "smoke": 180, "bench": 400, "trace": 400, "pmc": 240, "ab": 900, "valu": 240,
           "cmd": 600}
 
