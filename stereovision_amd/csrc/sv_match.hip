@@ -863,10 +863,28 @@ __device__ __forceinline__ uint32_t pk_sub16(uint32_t a, uint32_t b) {
 // packs' zero bytes add nothing), ΣL² once per step, ΣR² per disparity slot; the column cost
 // enters pre-shifted by dbits, (ΣL² + ΣR²) << dbits - ΣLR << (dbits + 1) by one
 // v_mad_i32_i24, and the window update is the same v_sad_u32.
-template <int R, int LPGT, bool DEFER, bool KEYS, bool SSD = false>
+// LDSMIN (32-lane groups, takes DEFER's place): the cross-lane fold runs through a per-wave
+// LDS scratch of 8 keys x 64 lanes (2 KiB at the start of the wave's LDS) instead of the DPP
+// reduce-scatter + permlane join.  A pair's 8 keys are stored as [key i][lane] (8
+// ds_write_addtid_b32, consecutive lanes on consecutive banks) after its second step; at the
+// top of the next step lane r loads the 8 dwords [8r, 8r + 8) = key r >> 3, group (r >> 2) & 1,
+// quarter r & 3 as two ds_read_b128, folds them with 3 v_min3 + 1 v_min at that step's end
+// and finishes over its quad with two quad-perm DPP mins: 6 VALU per pair.  The block is one
+// wave and a wave's LDS operations complete in order, so the store -> load order in the
+// program is all the synchronisation there is, and one pair's scratch serves both pairs.
+// The two 16-B halves are read in the order (r >> 3) & 1 picks: within a ds_read_b128 lane
+// group ({0-3,12-15,20-27}, ...) the lanes' 32-B strides then cover all 64 banks once.
+// Afterwards the four lanes of quad m hold key m >> 1 of group m & 1 for both pairs; odd
+// lanes take the second pair (one v_cndmask), lanes 0 and 1 of each quad emit: one store per
+// chunk, one chunk late, as with DEFER.
+typedef uint32_t lds_u32x4 __attribute__((ext_vector_type(4), may_alias));
+constexpr int RING_SCRATCH_BYTES = 8 * 64 * 4;
+
+template <int R, int LPGT, bool DEFER, bool KEYS, bool SSD = false, bool LDSMIN = false>
 __global__ __launch_bounds__(64, 2) void k_match_ring(MatchParams a) {
     using P = PackCfg<COST_SAD4, R>;
     constexpr int NW = P::NW, NC = P::NC, W2 = 2 * R + 1;
+    static_assert(!LDSMIN || (LPGT == 32 && R <= 5), "the LDS fold is laid out for two 32-lane groups of 32-bit keys");
     // PK (r 6..7): window and column costs of rows 2j, 2j+1 share a register as two u16
     // (a window costs at most 57375), updated with v_pk_add/sub_u16: 15 ring steps x 16
     // cells fit in 120 VGPRs; the argmin keys (cost << 16) | idx are built per step
@@ -913,7 +931,7 @@ __global__ __launch_bounds__(64, 2) void k_match_ring(MatchParams a) {
     const int NRlog = WC - S + Tn + 4 * LPG;
     constexpr int c0 = 1;                               // chunk starts (index = 3 mod 4) meet slot gaps
     const int NRphys = NRlog + (NRlog + c0) / RG_DPL + 1;
-    uint4* wbase = smem;
+    uint4* wbase = smem + (LDSMIN ? RING_SCRATCH_BYTES / 16 : 0);   // the packs follow the scratch
     typename P::CT* cbase = reinterpret_cast<typename P::CT*>(wbase + (size_t)(NL + NRphys));
     const PackOut<COST_SAD4, R> Lw{wbase, cbase};
     const PackOut<COST_SAD4, R> Rw{wbase + NL, cbase + NL};
@@ -993,20 +1011,26 @@ __global__ __launch_bounds__(64, 2) void k_match_ring(MatchParams a) {
     // branches around the reductions the allocator spilled ~1,000.)
     constexpr bool join2 = LPG >= 32;
     int pofs = 0;
-    if (join2) {
+    if (join2 && !LDSMIN) {
         const auto p = __builtin_amdgcn_permlane16_swap((uint32_t)lane, (uint32_t)lane + 64u, false, false);
         // min(p[0], p[1]) of a lane comes from the first operand's values iff both p[k] < 64
         pofs = (max(p[0], p[1]) < 64u) ? 0 : 2;
     }
     // step t emits column xs + t + eb (join2: the chunk starting at step t emits the lane's
     // pair at column xs + t + eb)
-    const int eb = ju - 2 * R + pofs;
+    // LDSMIN: lane r emits row r >> 4, step (r >> 3) & 1 of pair r & 1, for the segment of
+    // group (r >> 2) & 1 (not the group whose costs it computes)
+    const int eq = LDSMIN ? lane >> 4 : jq;
+    const int exs = LDSMIN ? xw + ((lane >> 2) & 1) * S : xs;
+    const int eb = (LDSMIN ? ((lane >> 3) & 1) + 2 * (lane & 1) : ju + pofs) - 2 * R;
     constexpr int OB = KEYS ? 4 : 2;                        // bytes per output element
-    const int ooff = OB * ((y + jq) * a.opitch + xs + eb);   // bytes
+    const int ooff = OB * ((y + eq) * a.opitch + exs + eb);   // bytes
     // 32-bit buffer offsets from one SGPR descriptor (no 64-bit per-lane addresses to keep)
     const auto orsrc = KEYS ? __builtin_amdgcn_make_buffer_rsrc(a.keys, 0, 0x7FFFFFFF, 0x00020000)
                             : __builtin_amdgcn_make_buffer_rsrc(a.out, 0, 0x7FFFFFFF, 0x00020000);
-    const int emax = ((l & 1) == 0 && l < (join2 ? 32 : 16) && y + jq < a.row1) ? max(0, min(S, a.X1 - xs)) : 0;
+    const int emax = (LDSMIN ? (lane & 2) == 0 && y + eq < a.row1
+                             : (l & 1) == 0 && l < (join2 ? 32 : 16) && y + jq < a.row1)
+                         ? max(0, min(S, a.X1 - exs)) : 0;
 
     // store of a reduced key for the chunk starting at step tt (join2) / of step tt
     auto emit_key = [&](uint32_t key, int tt) {
@@ -1044,6 +1068,23 @@ __global__ __launch_bounds__(64, 2) void k_match_ring(MatchParams a) {
     int tprev = -(1 << 24);
 #pragma unroll
     for (int i = 0; i < 8; ++i) dv[i] = 0xFFFFFFFFu;
+    // LDSMIN: the scratch as dwords; a lane stores at scr[64 i + lane] and loads its two
+    // 16-B halves at sra and srb (byte offsets 32 lane + 16 s and 32 lane + 16 (1 - s))
+    [[maybe_unused]] uint32_t* const scr = reinterpret_cast<uint32_t*>(smem);
+    // the scratch's LDS byte address (wave-uniform), the M0 base of the addtid stores
+    [[maybe_unused]] const uint32_t scr_m0 = __builtin_amdgcn_readfirstlane(
+        (uint32_t)(uintptr_t)(__attribute__((address_space(3))) uint32_t*)scr);
+    [[maybe_unused]] const lds_u32x4* const sra = reinterpret_cast<const lds_u32x4*>(scr + 8 * lane + 4 * ((lane >> 3) & 1));
+    [[maybe_unused]] const lds_u32x4* const srb = reinterpret_cast<const lds_u32x4*>(scr + 8 * lane + 4 * (1 - ((lane >> 3) & 1)));
+    auto lds_fold = [&](const lds_u32x4& p, const lds_u32x4& s) {
+        uint32_t m = min(min(p.x, p.y), p.z);
+        m = min(min(m, p.w), s.x);
+        m = min(min(m, s.y), s.z);
+        m = min(m, s.w);
+        m = min(m, (uint32_t)__builtin_amdgcn_update_dpp(0u, (int)m, 0xB1, 0xF, 0xF, false));   // l ^ 1
+        return min(m, (uint32_t)__builtin_amdgcn_update_dpp(0u, (int)m, 0x4E, 0xF, 0xF, false));   // l ^ 2
+    };
+    [[maybe_unused]] const bool pairB = (lane & 1) != 0;
 
     // whole bodies of U = 4*W2 steps, no exits inside a body (an exit per chunk made LLVM
     // shuffle the rings); the first body skips its first e0 chunks by a uniform branch
@@ -1061,6 +1102,12 @@ __global__ __launch_bounds__(64, 2) void k_match_ring(MatchParams a) {
                 rn[u] = ld<COST_SAD4, R, true>(rb + (ch * (RG_DPL + 1) + u));
                 const Pk<NW> Lc = LPF ? Lnext : ld<COST_SAD4, R, true>(lb + (4 * ch + u));
                 if constexpr (LPF) Lnext = ld<COST_SAD4, R, true>(lb + (4 * ch + u + 1));
+                // LDSMIN: the pair stored after the previous step (u 0: the previous chunk's
+                // second pair, or stale scratch before the first chunk), folded below
+                lds_u32x4 fa{}, fb{};
+                if constexpr (LDSMIN) {
+                    if ((u & 1) == 0) { fa = *sra; fb = *srb; }
+                }
                 // SSD: ΣL² of this step's left pack per output row, pre-shifted by dbits
                 uint32_t sqL[4];
                 if constexpr (SSD) {
@@ -1141,7 +1188,43 @@ __global__ __launch_bounds__(64, 2) void k_match_ring(MatchParams a) {
                         kq[k] = !PK ? h[k][q] : (q & 1) ? (h[k][q >> 1] & 0xFFFF0000u) | lab[k] : (h[k][q >> 1] << 16) | lab[k];
                     bk[q][u & 1] = min(min(kq[0], kq[1]), min(kq[2], kq[3]));
                 }
+                if constexpr (LDSMIN) {
+                    if (u == 2) {
+                        kA = lds_fold(fa, fb);
+                    } else if (u == 0) {   // the previous chunk is complete: one store for its 4 steps
+                        const uint32_t kB = lds_fold(fa, fb);
+                        emit_key(pairB ? kB : kA, tprev);
+                        tprev = t0;
+                    }
+                }
                 __builtin_amdgcn_sched_barrier(0);
+                if constexpr (LDSMIN) {
+                    if (u & 1) {   // steps u-1, u: key (row q, step j) of every lane to scr[2q + j][lane]
+                        // ds_write_addtid_b32 (address = M0 + offset + 4 lane: the scratch's own
+                        // layout) sends one data VGPR and no address per store, 8 dwords per
+                        // pair instead of the 12 of four ds_write2st64_b32 (which gave back most
+                        // of the fold's gain); no builtin has it.  The compiler's
+                        // lgkmcnt counts do not see these stores: LDS returns in order, so each
+                        // count still waits for at least what it meant to
+                        asm volatile("s_mov_b32 m0, %8\n\t"
+                                     "s_nop 0\n\t"   // SALU write of M0 -> LDS add-TID: 1 wait state
+                                     "ds_write_addtid_b32 %0\n\t"
+                                     "ds_write_addtid_b32 %1 offset:256\n\t"
+                                     "ds_write_addtid_b32 %2 offset:512\n\t"
+                                     "ds_write_addtid_b32 %3 offset:768\n\t"
+                                     "ds_write_addtid_b32 %4 offset:1024\n\t"
+                                     "ds_write_addtid_b32 %5 offset:1280\n\t"
+                                     "ds_write_addtid_b32 %6 offset:1536\n\t"
+                                     "ds_write_addtid_b32 %7 offset:1792\n\t"
+                                     :
+                                     : "v"(bk[0][0]), "v"(bk[0][1]), "v"(bk[1][0]), "v"(bk[1][1]), "v"(bk[2][0]),
+                                       "v"(bk[2][1]), "v"(bk[3][0]), "v"(bk[3][1]), "s"(scr_m0)
+                                     : "memory", "m0");
+                        // wavefront scope: no instruction, keeps the next step's loads below
+                        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+                    }
+                    continue;
+                }
                 // steps u-1, u: 8 keys (row q, step j) at v[2q + j].  Warm-up pairs are reduced
                 // too (their keys are not emitted): no branch, so a chunk is one basic block and
                 // the scheduler can interleave a reduction's DPP / permlane chain with the next
@@ -1180,7 +1263,10 @@ __global__ __launch_bounds__(64, 2) void k_match_ring(MatchParams a) {
         rb = rb + NCH * (RG_DPL + 1);
         lb = lb + U;
     }
-    if (DEFER) {   // the last chunk's second pair
+    if constexpr (LDSMIN) {   // the last chunk's second pair and store
+        const uint32_t kB = lds_fold(*sra, *srb);
+        emit_key(pairB ? kB : kA, tprev);
+    } else if (DEFER) {   // the last chunk's second pair
         reduce_scatter8_bm(dv, lane & 15);
         if (join2) emit_key(join_pairs(kA, dv[0]), tprev);
         else emit_key(join_rows(dv[0]), tprev + 2);
@@ -1259,12 +1345,23 @@ bool ring_kind(int cost, int win, int num_disp) {
            (win <= 11 || (win <= 15 && num_disp % 4 == 0));
 }
 int ring_lpg(int num_disp) { return num_disp <= 64 ? 16 : num_disp <= 128 ? 32 : 64; }
+// LDS argmin fold (k_match_ring's LDSMIN): 32-lane groups at r 4, the SAD ring's disparity
+// output.  SV_RING_LDSMIN=0 (A/B) restores the DPP reduce-scatter.  Its 2 KiB scratch counts
+// in the wave's LDS: 1080p D=128 win 9 takes 18,144 + 2,048 = 20,192 B, still 8 waves per CU
+// (profiles/r07_ldsmin).
+bool ring_ldsmin(int lpg, int r, bool keys, bool ssd) {
+    static const bool on = [] {
+        const char* e = std::getenv("SV_RING_LDSMIN");
+        return !(e && e[0] == '0');
+    }();
+    return on && lpg == 32 && r == 4 && !keys && !ssd;
+}
 // Segment width per group: S (a multiple of 4) minimising the steps all waves of a row
 // run, ceil(band / (G*S)) * (S + 2r) (idle columns of the last wave + the 2r warm-up steps
 // of every segment), among segments whose LDS leaves room for 2 waves per SIMD; ties go to
 // the longer segment.  SV_RING_SEG=<S> forces a width (A/B measurements).
-size_t ring_lds_bytes(int lpg, int seg, int r);
-int ring_seg(int lpg, int r, int band, long long blocks) {
+size_t ring_lds_bytes(int lpg, int seg, int r, bool ldsmin);
+int ring_seg(int lpg, int r, int band, long long blocks, bool ldsmin) {
     static const int env = [] {
         const char* e = std::getenv("SV_RING_SEG");
         const int v = e ? std::atoi(e) : 0;
@@ -1276,18 +1373,18 @@ int ring_seg(int lpg, int r, int band, long long blocks) {
     int best = 8;
     long long best_cost = -1;
     for (int S = 8; S <= 1024; S += 4) {
-        if (S > 8 && ring_lds_bytes(lpg, S, r) > 20 * 1024) break;
+        if (S > 8 && ring_lds_bytes(lpg, S, r, ldsmin) > 20 * 1024) break;
         const long long cost = (long long)((band + G * S - 1) / (G * S)) * ((S + 2 * r + 3) & ~3);
         if (best_cost < 0 || cost <= best_cost) { best = S; best_cost = cost; }
     }
     return best;
 }
-size_t ring_lds_bytes(int lpg, int seg, int r) {
+size_t ring_lds_bytes(int lpg, int seg, int r, bool ldsmin) {
     const int wc = (64 / lpg) * seg;
     const int tn = (seg + 2 * r + 3) & ~3;
     const int nl = wc - seg + tn + 1, nr = wc - seg + tn + 4 * lpg;
     const int nrp = nr + (nr + 1) / RG_DPL + 1;
-    return (size_t)(nl + nrp) * (r <= 3 ? 20 : r <= 5 ? 24 : 28);
+    return (size_t)(nl + nrp) * (r <= 3 ? 20 : r <= 5 ? 24 : 28) + (ldsmin ? RING_SCRATCH_BYTES : 0);
 }
 
 template <int R, int LPG, bool KEYS, bool SSD>
@@ -1301,12 +1398,26 @@ int launch_ring_rl(const MatchParams& a, size_t lds, hipStream_t s) {
     if constexpr (SSD) fn = k_match_ring<R, LPG, R != 5, false, true>;
     else if constexpr (KEYS) fn = k_match_ring<R, LPG, R != 5, true>;
     else fn = (defer && R != 5) ? k_match_ring<R, LPG, R != 5, false> : k_match_ring<R, LPG, false, false>;
+    if constexpr (R == 4 && LPG == 32 && !KEYS && !SSD) {
+        if (ring_ldsmin(LPG, R, KEYS, SSD)) fn = k_match_ring<R, LPG, false, false, false, true>;
+    }
     if (lds > 65536) {
         hipError_t e = hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) return (int)e;
     }
     const int wc = (64 / a.lpg) * a.segm;
     dim3 grid((a.X1 - a.X0 + wc - 1) / wc, (a.row1 - a.row0 + 3) / 4, a.nf > 1 ? a.nf : 1);
+    // SV_RING_OCC=1: print every ring launch's resident waves per CU at its LDS size
+    static const bool occ = [] {
+        const char* e = std::getenv("SV_RING_OCC");
+        return e && e[0] == '1';
+    }();
+    if (occ) {
+        int nb = -1;
+        (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void*)fn, 64, lds);
+        std::fprintf(stderr, "k_match_ring r=%d lpg=%d ldsmin=%d seg=%d lds=%zu B: %d waves/CU\n", R, LPG,
+                     (int)ring_ldsmin(LPG, R, KEYS, SSD), a.segm, lds, nb);
+    }
     // SV_XCD_MAP=0 (A/B): tiles in plain dispatch order
     static const bool xcd = [] {
         const char* e = std::getenv("SV_XCD_MAP");
@@ -1334,8 +1445,9 @@ int launch_ring(const MatchParams& a0, hipStream_t s) {
     a.lpg_log2 = a.lpg == 16 ? 4 : a.lpg == 32 ? 5 : 6;
     a.dbits = SSD ? a.lpg_log2 + 2 : 16;   // SSD keys: (cost << log2(4 LPG)) | idx
     if (SSD) a.pad_key = (uint32_t)((max_cost(a.win, COST_SSD) + 1) << a.dbits);
-    a.segm = ring_seg(a.lpg, a.r, a.X1 - a.X0, (long long)((a.row1 - a.row0 + 3) / 4) * (a.nf > 1 ? a.nf : 1));
-    const size_t lds = ring_lds_bytes(a.lpg, a.segm, a.r);
+    const bool ldsmin = ring_ldsmin(a.lpg, a.r, KEYS, SSD);
+    a.segm = ring_seg(a.lpg, a.r, a.X1 - a.X0, (long long)((a.row1 - a.row0 + 3) / 4) * (a.nf > 1 ? a.nf : 1), ldsmin);
+    const size_t lds = ring_lds_bytes(a.lpg, a.segm, a.r, ldsmin);
     if (lds > 160 * 1024) return (int)hipErrorInvalidValue;
     if constexpr (SSD) {
         switch (a.r) {
