@@ -390,7 +390,7 @@ __device__ __forceinline__ void build_all_packs(const MatchParams& a, int y, int
 // the row loads of up to MF of its 4-column groups before it transposes any of them, so a
 // wave waits for its global loads once per MF groups instead of once per group (the
 // per-group form left ~8% of k_match's time in the segment prologue).  Groups touching the
-// image border load from column 0 (unused) and take build_pack afterwards.
+// image border load nothing and take build_pack afterwards.
 template <int R, int MF, int DPL>
 __device__ __forceinline__ void build_ring_packs(const MatchParams& a, int y, int cL0, int NL, int cR0,
                                                  int NRlog, int c0, PackOut<COST_SAD4, R> Lp,
@@ -398,16 +398,25 @@ __device__ __forceinline__ void build_ring_packs(const MatchParams& a, int y, in
     constexpr int NW = PackCfg<COST_SAD4, R>::NW, NRW = 2 * R + 4;
     const bool aligned = ((reinterpret_cast<uintptr_t>(a.L) | reinterpret_cast<uintptr_t>(a.R) |
                            (uintptr_t)a.pitch) & 3u) == 0;
-    if (!aligned) {
+    // the row loads below address a frame by 32-bit byte offsets
+    const bool near = (long long)a.H * (long long)a.pitch < 0x7FFFFFFFLL;
+    if (!aligned || !near) {
         build_all_packs<COST_SAD4, R, DPL>(a, y, cL0, NL, cR0, NRlog, c0, Lp, Rp, lane);
         return;
     }
+    // Row loads through one buffer descriptor per image: the row offset (wave-uniform) is the
+    // scalar offset and the group's first column the only per-lane term, instead of a 64-bit
+    // per-lane address for every (group, row).  A wave's m-th groups are the left image's, the
+    // right image's or (one m per wave) both: each image's lanes load in a pass of their own,
+    // and a pass with no lanes is skipped.
+    const auto lsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t*>(a.L), 0, 0x7FFFFFFF, 0x00020000);
+    const auto rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t*>(a.R), 0, 0x7FFFFFFF, 0x00020000);
     const int aL = cL0 & ~3, aR = cR0 & ~3;                  // floor to a multiple of 4
     const int gL = (cL0 + NL - aL + 3) >> 2, gR = (cR0 + NRlog - aR + 3) >> 2;
     const int G = gL + gR;
-    uint32_t roff[NRW];                                      // row offsets (wave-uniform)
+    int roff[NRW];                                           // row offsets (wave-uniform)
 #pragma unroll
-    for (int j = 0; j < NRW; ++j) roff[j] = (uint32_t)clampi(y - R + j, 0, a.H - 1) * (uint32_t)a.pitch;
+    for (int j = 0; j < NRW; ++j) roff[j] = clampi(y - R + j, 0, a.H - 1) * a.pitch;
     for (int g0 = 0; g0 < G; g0 += 64 * MF) {
         uint32_t rw[MF][NRW];
 #pragma unroll
@@ -415,10 +424,15 @@ __device__ __forceinline__ void build_ring_packs(const MatchParams& a, int y, in
             const int gi = g0 + lane + 64 * m;
             const bool right = gi >= gL;
             const int cg = right ? aR + 4 * (gi - gL) : aL + 4 * gi;
-            const bool in = gi < G && cg >= 0 && cg + 4 <= a.W;
-            const uint8_t* img = (right ? a.R : a.L) + (in ? cg : 0);
+            const bool in = gi < G && cg >= 0 && cg + 4 <= a.W;   // the others' rw stay unread
+            if (in && !right) {
 #pragma unroll
-            for (int j = 0; j < NRW; ++j) rw[m][j] = *reinterpret_cast<const uint32_t*>(img + roff[j]);
+                for (int j = 0; j < NRW; ++j) rw[m][j] = __builtin_amdgcn_raw_buffer_load_b32(lsrc, cg, roff[j], 0);
+            }
+            if (in && right) {
+#pragma unroll
+                for (int j = 0; j < NRW; ++j) rw[m][j] = __builtin_amdgcn_raw_buffer_load_b32(rsrc, cg, roff[j], 0);
+            }
         }
 #pragma unroll
         for (int m = 0; m < MF; ++m) {
@@ -837,7 +851,8 @@ __global__ __launch_bounds__((64 * PackCfg<COST, ND>::WPB), (Occ<COST, ND>::W)) 
 // + 4 v_sad_u32 per 4 cells (key = |key - leaving| + entering; r 5 on 16/64-lane groups: 4
 // v_sub + 4 v_add).  Both rings (the M-slot cost ring and the 4-deep right pack ring) have
 // static register indices inside a body of lcm(4, M) unrolled steps.
-// The first 2r steps of a segment fill the window (ring starts at zero) and emit nothing.
+// The first 2r steps of a segment fill the window and emit nothing: whole chunks of them run
+// ahead of the loop in an add-only variant (no leaving cost, no argmin), see `chunk` below.
 // Keys are (cost << 16) | idx; padding disparities (idx >= D)
 // start at cost 0x8000, above every real window cost (<= 121*255 = 30855 for win 11).
 constexpr int RG_DPL = 4;
@@ -978,13 +993,16 @@ __global__ __launch_bounds__(64, 2) void k_match_ring(MatchParams a) {
 #pragma unroll
         for (int q = 0; q < RQ; ++q) h[k][q] = base;
     }
+    // No slot is read before a step has written it or the last warm-up chunk has zeroed it
+    // (below), so the ring starts with whatever its registers hold: the empty asm gives every
+    // element a defined value at no instruction (M * 16 v_mov per wave otherwise).
     uint32_t ring[M][RG_DPL][RQ];
 #pragma unroll
     for (int s = 0; s < M; ++s)
 #pragma unroll
         for (int k = 0; k < RG_DPL; ++k)
 #pragma unroll
-            for (int q = 0; q < RQ; ++q) ring[s][k][q] = 0u;
+            for (int q = 0; q < RQ; ++q) asm volatile("" : "=v"(ring[s][k][q]));
     Pk<NW> rn[RG_DPL];
 #pragma unroll
     for (int s = 1; s < RG_DPL; ++s) rn[RG_DPL - s] = ld<COST_SAD4, R, true>(Rp + rslot(iR0 - s, c0, RG_DPL));
@@ -1086,13 +1104,20 @@ __global__ __launch_bounds__(64, 2) void k_match_ring(MatchParams a) {
     };
     [[maybe_unused]] const bool pairB = (lane & 1) != 0;
 
-    // whole bodies of U = 4*W2 steps, no exits inside a body (an exit per chunk made LLVM
-    // shuffle the rings); the first body skips its first e0 chunks by a uniform branch
-    for (int it = 0, t0 = -4 * e0; it < nit; ++it) {
-#pragma unroll
-        for (int ch = 0; ch < NCH; ++ch, t0 += 4) {
-            if (t0 < 0) continue;            // the first body's skipped chunks (uniform)
-            uint32_t bk[4][2];
+    // One chunk (4 steps) at body position ch, first step t0, in two compile-time variants.
+    // WARM: all four steps lie in the warm-up (t0 + 3 < 2r).  Their argmins would be emitted
+    // out of range and the costs leaving their windows are the ring's initial zeros, so the
+    // variant only adds the entering costs to the keys and files them in the ring (the same
+    // static slots and right-pack names as the normal variant of this position): no read of
+    // the ring, no min, no fold, no scratch traffic, no store.  tprev, kA and dv keep their
+    // sentinels, so the first normal chunk is the sentinel first chunk.  The last warm-up
+    // chunk zeroes the slots that steps 4*nwarm .. 2r read before any step has written them
+    // (one step's slot for even r, three for odd r); warm-up steps that share a chunk with
+    // output steps (step 8 at r 4) run in the normal variant against those zeros.
+    constexpr int NZ = 2 * R - 4 * (2 * R / 4) + 1;
+    auto chunk = [&](auto warm_c, const int ch, const int t0) __attribute__((always_inline)) {
+            constexpr bool WARM = decltype(warm_c)::value;
+            [[maybe_unused]] uint32_t bk[4][2];
 #pragma unroll
             for (int u = 0; u < 4; ++u) {
                 // the entering cost goes to `slot`, the leaving one (entered W2 steps ago)
@@ -1105,7 +1130,7 @@ __global__ __launch_bounds__(64, 2) void k_match_ring(MatchParams a) {
                 // LDSMIN: the pair stored after the previous step (u 0: the previous chunk's
                 // second pair, or stale scratch before the first chunk), folded below
                 lds_u32x4 fa{}, fb{};
-                if constexpr (LDSMIN) {
+                if constexpr (LDSMIN && !WARM) {
                     if ((u & 1) == 0) { fa = *sra; fb = *srb; }
                 }
                 // SSD: ΣL² of this step's left pack per output row, pre-shifted by dbits
@@ -1120,7 +1145,7 @@ __global__ __launch_bounds__(64, 2) void k_match_ring(MatchParams a) {
                 }
                 // !SADU: the leaving column's costs need no LDS data: subtract them while the
                 // loads are in flight; k = 0 (the fresh right pack) last
-                if constexpr (!SADU) {
+                if constexpr (!SADU && !WARM) {
 #pragma unroll
                     for (int k = 0; k < RG_DPL; ++k)
 #pragma unroll
@@ -1143,7 +1168,7 @@ __global__ __launch_bounds__(64, 2) void k_match_ring(MatchParams a) {
                             const uint32_t c = __builtin_amdgcn_sad_hi_u8(
                                 Lc.w[NC + 2 * j + 1], Rk.w[NC + 2 * j + 1],
                                 __builtin_amdgcn_sad_u8(Lc.w[NC + 2 * j], Rk.w[NC + 2 * j], cn));
-                            if constexpr (SADU) sad_u32_acc(h[k][j], ring[oslot][k][j], c);
+                            if constexpr (SADU && !WARM) sad_u32_acc(h[k][j], ring[oslot][k][j], c);
                             else h[k][j] = pk_add16(h[k][j], c);
                             ring[slot][k][j] = c;
                         }
@@ -1160,7 +1185,8 @@ __global__ __launch_bounds__(64, 2) void k_match_ring(MatchParams a) {
                             const uint32_t rr = __builtin_amdgcn_udot4(Rk.w[NC + q], Rk.w[NC + q], sr, false);
                             const uint32_t t = (rr << a.dbits) + sqL[q];
                             const uint32_t c = (uint32_t)__mul24((int)lr, -(2 << a.dbits)) + t;
-                            sad_u32_acc(h[k][q], ring[oslot][k][q], c);
+                            if constexpr (WARM) h[k][q] += c;
+                            else sad_u32_acc(h[k][q], ring[oslot][k][q], c);
                             ring[slot][k][q] = c;
                         }
                     } else {
@@ -1174,11 +1200,15 @@ __global__ __launch_bounds__(64, 2) void k_match_ring(MatchParams a) {
                             // + entering): the key holds the leaving column's cost as one of
                             // its summands, so key >= leaving and the absolute value is the
                             // plain difference (one VOP3 instead of a VOP2 sub + add)
-                            if constexpr (SADU) sad_u32_acc(h[k][q], ring[oslot][k][q], c);
+                            if constexpr (SADU && !WARM) sad_u32_acc(h[k][q], ring[oslot][k][q], c);
                             else h[k][q] += c;
                             ring[slot][k][q] = c;
                         }
                     }
+                }
+                if constexpr (WARM) {
+                    __builtin_amdgcn_sched_barrier(0);
+                    continue;
                 }
 #pragma unroll
                 for (int q = 0; q < 4; ++q) {
@@ -1259,6 +1289,35 @@ __global__ __launch_bounds__(64, 2) void k_match_ring(MatchParams a) {
                     }
                 }
             }
+            if constexpr (WARM) {
+                if (t0 + 7 >= 2 * R) {   // the last warm-up chunk
+#pragma unroll
+                    for (int i = 0; i < NZ; ++i)
+#pragma unroll
+                        for (int k = 0; k < RG_DPL; ++k)
+#pragma unroll
+                            for (int q = 0; q < RQ; ++q) ring[(4 * ch + 5 + i) % M][k][q] = 0u;
+                }
+            }
+    };
+    // The warm-up chunks run ahead of the loop, one copy per entry chunk e0 (positions past
+    // the body's end are the second body's: same slot names, since U is a multiple of M, and
+    // the pointers are body 0's).  Inside the loop a third path per chunk made LLVM copy the
+    // keys and the pack rings at every merge.
+    constexpr int NWARM = 2 * R / 4;
+#pragma unroll
+    for (int e = 0; e < NCH; ++e) {
+        if (e != e0) continue;               // (uniform)
+#pragma unroll
+        for (int i = 0; i < NWARM; ++i) chunk(std::true_type{}, e + i, 4 * i);
+    }
+    // whole bodies of U = 4*W2 steps, no exits inside a body (an exit per chunk made LLVM
+    // shuffle the rings); the first body skips its first e0 chunks by a uniform branch
+    for (int it = 0, t0 = -4 * e0; it < nit; ++it) {
+#pragma unroll
+        for (int ch = 0; ch < NCH; ++ch, t0 += 4) {
+            if (t0 < 4 * NWARM) continue;    // skipped and warm-up chunks of the first bodies (uniform)
+            chunk(std::false_type{}, ch, t0);
         }
         rb = rb + NCH * (RG_DPL + 1);
         lb = lb + U;
