@@ -53,6 +53,7 @@ SgbmParams sgbm_reference_params(int win) {
 int enqueue_speckles(sv_ctx* c, int16_t* d_img, int H, int W, int pitch, int new_val, int max_speckle_size,
                      int max_diff, hipStream_t s, int nf, long long fimg) {
     if (max_speckle_size <= 0) return 0;
+    c->scratch_written(d_img);
     const size_t n = (size_t)H * W * (nf < 1 ? 1 : nf);
     SV_HIP(c->cc_parent.ensure(n * 4));
     SV_HIP(c->cc_size.ensure(n * 4));
@@ -86,6 +87,7 @@ int enqueue_sgbm(sv_ctx* c, const uint8_t* L, const uint8_t* R, int H, int W, in
                  int num_disp, int win, SgbmParams p, int16_t* out, int opitch, hipStream_t s, int nf,
                  long long fs_in, long long fs_out) {
     if (nf < 1) nf = 1;
+    c->scratch_written(out);
     if (sv::sgbm_dp(num_disp) < 0) return fail(SV_EINVAL, "num_disp must be in [1, 512]");
     if (W > 16384) return fail(SV_EINVAL, "SGBM: width beyond 16384");
     if (p.P1 < 0 || p.P2 < 0) return fail(SV_EINVAL, "negative P1/P2");
@@ -181,13 +183,16 @@ int enqueue_sgbm(sv_ctx* c, const uint8_t* L, const uint8_t* R, int H, int W, in
 int enqueue_disparity(sv_ctx* c, const uint8_t* L, const uint8_t* R, int H, int W, int pitch,
                       int min_disp, int num_disp, int win, int cost, int row0, int row1,
                       int16_t* out, int opitch, hipStream_t s, int nf, long long fs_in,
-                      long long fs_out) {
+                      long long fs_out, bool track_margins) {
     sv::MatchPlan plan;
     int rc = check_match(H, W, min_disp, num_disp, win, cost, &plan);
     if (rc) return rc;
     if (row0 < 0) row0 = 0;
     if (row1 > H) row1 = H;
     if (row1 <= row0) return 0;
+    // whatever this call writes, d16's margins count as unknown until its launch is enqueued
+    const sv_ctx::MarginKey had = c->d16_margins;
+    c->scratch_written(out);
     if (cost == SV_COST_SGBM) {   // the top-down path crosses rows: whole frames only
         if (row0 != 0 || row1 != H) return fail(SV_EINVAL, "SGBM cannot compute a row band (use frames)");
         return enqueue_sgbm(c, L, R, H, W, pitch, min_disp, num_disp, win, sgbm_reference_params(win), out, opitch,
@@ -240,7 +245,26 @@ int enqueue_disparity(sv_ctx* c, const uint8_t* L, const uint8_t* R, int H, int 
         a.keys = c->keys.as<uint32_t>();
         a.keys_stride = ke;
     }
+    // a whole-frame launch into the scratch map: every kind writes the margins of all nf frames,
+    // so later launches with this key may skip them; this one skips them if an earlier one did
+    sv_ctx::MarginKey key;
+    if (track_margins && out == c->d16.as<int16_t>() && row0 == 0 && row1 == H) {
+        key.valid = true;
+        key.p = c->d16.p;
+        key.gen = c->d16.gen;
+        key.H = H;
+        key.W = W;
+        key.opitch = opitch;
+        key.X0 = a.X0;
+        key.X1 = a.X1;
+        key.min_disp = min_disp;
+        key.nf = a.nf;
+        key.fs_out = fs_out;
+        a.margins_done = had.covers(key) ? 1 : 0;
+        if (a.margins_done) key = had;   // (also the frames past a shorter batch keep theirs)
+    }
     SV_LAUNCH(c, SV_K_MATCH, s, sv::launch_match(a, plan, cost, s));
+    if (key.valid) c->d16_margins = key;
     return 0;
 }
 
@@ -251,6 +275,7 @@ int enqueue_disparity(sv_ctx* c, const uint8_t* L, const uint8_t* R, int H, int 
 int attach_lut(sv_ctx* c, sv::PostParams& pp, hipStream_t s, bool whole) {
     pp.lut_n = 0;
     pp.lut_shift = 0;
+    pp.lut_cap = 0;
     if (pp.mode == SV_POST_NONE || pp.num_disp <= 0 || pp.num_disp > 512) return 0;
     sv_ctx::LutKey k;
     k.mode = pp.mode;
@@ -269,7 +294,9 @@ int attach_lut(sv_ctx* c, sv::PostParams& pp, hipStream_t s, bool whole) {
     const size_t n = (size_t)k.n;
     float* la = buf.as<float>();
     if (!(k == key) || !ev) {
-        SV_HIP(buf.ensure(n * (2 * sizeof(float) + 1)));
+        // (the whole-disparity table: lut_b and lut_u8 start n entries into the buffer and the
+        // median's unchecked lookups may index kLutWholeSpan entries of each)
+        SV_HIP(buf.ensure(whole ? (n + sv::kLutWholeSpan) * 2 * sizeof(float) : n * (2 * sizeof(float) + 1)));
         la = buf.as<float>();
         if (!ev) SV_HIP(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
         int e = sv::launch_post_lut(pp, k.m0, k.n, whole ? 16 : 1, la, reinterpret_cast<uint8_t*>(la + 2 * n), la + n,
@@ -287,6 +314,7 @@ int attach_lut(sv_ctx* c, sv::PostParams& pp, hipStream_t s, bool whole) {
     pp.lut_m0 = k.m0;
     pp.lut_n = k.n;
     pp.lut_shift = whole ? 4 : 0;
+    pp.lut_cap = whole ? k.n + sv::kLutWholeSpan : k.n;   // (the allocation above)
     return 0;
 }
 
@@ -602,6 +630,7 @@ int sv_release_scratch(sv_ctx* c) {
                       &c->sg_l, &c->sg_lt, &c->sg_band, &c->sg_rec, &c->cc_parent, &c->cc_size, &c->m16,
                       &c->gm16, &c->keys};
     for (auto* b : bufs) b->release();
+    c->d16_margins.valid = false;   // (d16's generation has changed as well)
     return 0;
 }
 

@@ -109,8 +109,9 @@ int sv_depth_map_batch_dev(sv_ctx* c, const uint8_t* d_left, const uint8_t* d_ri
         d16 = c->d16.as<int16_t>();
     }
     if (match) {
+        // (the scratch map's invalid margins are written once per geometry: d16_margins)
         const int rc = enqueue_disparity(c, d_left, d_right, H, W, pitch, min_disp, num_disp, win, cost, 0, H, d16, W,
-                                         s, n_frames, frame_stride, fs);
+                                         s, n_frames, frame_stride, fs, !d_disp16);
         if (rc) return rc;
     }
     if (!median) return 0;
@@ -118,6 +119,11 @@ int sv_depth_map_batch_dev(sv_ctx* c, const uint8_t* d_left, const uint8_t* d_ri
     float* disp = nullptr;
     int rc = map_out_post(c, out, min_disp, num_disp, cost, true, s, &pp, &disp);
     if (rc) return rc;
+    // the maps are this call's own integer-matcher output and the whole-disparity table covers
+    // every value they can hold: the epilogue looks up unchecked.  Maps handed in (the median
+    // stage alone) and SGBM's keep the checked form
+    pp.lut_unchecked = match && cost != SV_COST_SGBM && pp.lut_shift == 4 && pp.lut_m0 == (min_disp - 1) * 16 &&
+                       pp.lut_n == num_disp + 1;
     const long long fin = n_frames > 1 ? frame_stride : 0;
     if (out->harris && (W < 8 || H < 8)) {   // the DPP form needs 8 px a side: a launch of its own
         SV_LAUNCH(c, SV_K_MEDIAN, s, sv::launch_median_i16(d16, H, W, 0, H, disp, pp, s, n_frames, fs, fs));
@@ -1203,6 +1209,7 @@ int sv_filter_speckles(sv_ctx* c, int16_t* img, int H, int W, int new_val, int m
     SV_HIP(c->d16.ensure(bytes));
     SV_HIP(c->hin.ensure(bytes));
     std::memcpy(c->hin.p, img, bytes);
+    c->scratch_written(c->d16.p);
     SV_HIP(hipMemcpyAsync(c->d16.p, c->hin.p, bytes, hipMemcpyHostToDevice, c->stream));
     const int rc = enqueue_speckles(c, c->d16.as<int16_t>(), H, W, W, new_val, max_speckle_size, max_diff, c->stream);
     if (rc) return rc;

@@ -49,8 +49,12 @@ using svc::hipfail;
 struct DevBuf {
     void* p = nullptr;
     size_t cap = 0;
+    // counts the allocations and releases: what a caller remembers about the buffer's contents
+    // holds only while `gen` stands (hipMalloc may hand back the address it has just freed)
+    unsigned long long gen = 0;
     hipError_t ensure(size_t n) {
         if (n <= cap) return hipSuccess;
+        ++gen;
         if (p) (void)hipFree(p);
         p = nullptr;
         cap = 0;
@@ -59,6 +63,7 @@ struct DevBuf {
         return e;
     }
     void release() {
+        ++gen;
         if (p) (void)hipFree(p);
         p = nullptr;
         cap = 0;
@@ -151,6 +156,31 @@ struct sv_ctx {
     hipEvent_t lutw_ev = nullptr;
     hipStream_t lutw_stream = nullptr;
     HostBuf hin, hout;
+    // Invalid margins of the scratch map d16 (sv_depth_map_batch_dev without a caller's map):
+    // the columns outside the matched band hold (min_disp - 1) * 16 in every launch of one
+    // geometry, so once a whole-frame launch has written them the next launches with the same
+    // key leave them alone (MatchParams::margins_done).  `valid` falls with every other write
+    // into d16 (scratch_written); a release or reallocation of d16 changes its generation, which
+    // is part of the key.
+    struct MarginKey {
+        bool valid = false;
+        const void* p = nullptr;
+        unsigned long long gen = 0;
+        int H = 0, W = 0, opitch = 0, X0 = 0, X1 = 0, min_disp = 0, nf = 0;
+        long long fs_out = 0;
+        bool covers(const MarginKey& o) const {   // a launch with key o may rely on these margins
+            return valid && p == o.p && gen == o.gen && H == o.H && W == o.W && opitch == o.opitch &&
+                   X0 == o.X0 && X1 == o.X1 && min_disp == o.min_disp && nf >= o.nf &&
+                   (o.nf <= 1 || fs_out == o.fs_out);
+        }
+    } d16_margins;
+    // a write into [out, ...) that is not a margin-tracked launch: forget d16's margins when
+    // `out` lies inside d16
+    void scratch_written(const void* out) {
+        const char* b = static_cast<const char*>(d16.p);
+        const char* o = static_cast<const char*>(out);
+        if (b && o >= b && o < b + d16.cap) d16_margins.valid = false;
+    }
     // Cross-stream ordering of the context's scratch (d16, the post table, HOG histograms,
     // SGBM volumes, reduction accumulators): `*_dev` calls may pass any stream, so a call on
     // stream s first waits for the event recorded after the previous scratch user when that
@@ -254,11 +284,13 @@ int enqueue_sgbm(sv_ctx* c, const uint8_t* L, const uint8_t* R, int H, int W, in
                  int num_disp, int win, SgbmParams p, int16_t* out, int opitch, hipStream_t s, int nf = 1,
                  long long fs_in = 0, long long fs_out = 0);
 // Disparity for rows [row0,row1) of gray device images; nf > 1: a batch of frames, frame z at
-// L/R + z*fs_in bytes and out + z*fs_out elements.
+// L/R + z*fs_in bytes and out + z*fs_out elements.  track_margins: `out` is the context's
+// scratch map d16 and this is a whole-frame launch whose invalid margins may be left as an
+// earlier launch of the same geometry wrote them (sv_ctx::d16_margins).
 int enqueue_disparity(sv_ctx* c, const uint8_t* L, const uint8_t* R, int H, int W, int pitch,
                       int min_disp, int num_disp, int win, int cost, int row0, int row1,
                       int16_t* out, int opitch, hipStream_t s, int nf = 1, long long fs_in = 0,
-                      long long fs_out = 0);
+                      long long fs_out = 0, bool track_margins = false);
 // Attach the cached post-processing table (whole: the map holds whole disparities only).
 int attach_lut(sv_ctx* c, sv::PostParams& pp, hipStream_t s, bool whole = false);
 // Device copy of a 256-entry BGR colormap table (re-uploaded only when it changes).

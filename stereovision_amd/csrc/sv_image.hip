@@ -791,6 +791,19 @@ __device__ __forceinline__ PostVals post_median(const PostParams& pp, int mv) {
     }
     return post_vals(pp, (float)mv / 16.0f);
 }
+// ... of a map whose values are all entries of the whole-disparity table (PostParams::
+// lut_unchecked): no range or multiple test and no exact path beside the lookup.  The index
+// keeps 12 bits (one v_bfe_u32 in the shift's place) and the host allocates the table for
+// kLutWholeSpan entries, so a map that breaks the promise reads unset entries, never memory
+// outside the table.
+__device__ __forceinline__ PostVals post_median_whole(const PostParams& pp, int mv) {
+    const uint32_t li = ((uint32_t)(mv - pp.lut_m0) >> 4) & (uint32_t)(kLutWholeSpan - 1);
+    PostVals o;
+    o.a = at(pp.lut_a, li);
+    o.u = at(pp.lut_u8, li);
+    o.b = pp.mode == POST_SCALED ? at(pp.lut_b, li) : 0.0f;
+    return o;
+}
 
 // Post-processing of an int16 x16 median map (the value OpenCV's fixed-point disparity holds
 // after medianBlur, depth_map.py:909-912) into create_depth_map's outputs (depth_map.py:
@@ -850,7 +863,8 @@ __global__ __launch_bounds__(256) void k_post_m16(const int16_t* __restrict__ in
 
 // HF: the Harris blocks this instance carries (0 none, 1 60-column waves, 2 248-column waves):
 // the 248-column form needs 81 VGPRs, which would cost the plain median (36) its occupancy
-template <int HF>
+// WH: the epilogue's table lookups are unchecked (PostParams::lut_unchecked)
+template <int HF, bool WH>
 __global__ __launch_bounds__(256) void k_median_i16(const int16_t* __restrict__ in, int H, int W,
                                                     int row0, int row1, float* __restrict__ disp,
                                                     PostParams pp, long long fs_in, long long fs_out,
@@ -1046,6 +1060,13 @@ __global__ __launch_bounds__(256) void k_median_i16(const int16_t* __restrict__ 
     med[tb + 2][tx >> 1] = mp[2];
     med[tb + 3][tx >> 1] = mp[3];
     __syncthreads();
+    auto post = [&](int mv) { return WH ? post_median_whole(pp, mv) : post_median(pp, mv); };
+    // the outputs allow 4-pixel stores (uniform; with W % 4 == 0 a thread's 4 columns are all
+    // inside the row or all outside)
+    const bool vec = (W & 3) == 0 &&
+                     (((uintptr_t)disp | (uintptr_t)pp.out_a | (uintptr_t)pp.out_b) & 15) == 0 &&
+                     (((uintptr_t)pp.out_u8 | (uintptr_t)pp.out_bgr | (uintptr_t)pp.out_d8) & 3) == 0 &&
+                     ((uintptr_t)pp.out_m16 & 7) == 0;
 #pragma unroll
     for (int pass = 0; pass < 2; ++pass) {
         const int r = (int)(threadIdx.x >> 5) + 8 * pass, c4 = (int)(threadIdx.x & 31) * 4;
@@ -1055,10 +1076,6 @@ __global__ __launch_bounds__(256) void k_median_i16(const int16_t* __restrict__ 
         const int mv[4] = {(int)(int16_t)(raw.x & 0xFFFF), (int)(int16_t)(raw.x >> 16),
                            (int)(int16_t)(raw.y & 0xFFFF), (int)(int16_t)(raw.y >> 16)};
         const uint32_t i = (uint32_t)y * W + x;
-        const bool vec = x + 3 < W && (W & 3) == 0 &&
-                         (((uintptr_t)disp | (uintptr_t)pp.out_a | (uintptr_t)pp.out_b) & 15) == 0 &&
-                         (((uintptr_t)pp.out_u8 | (uintptr_t)pp.out_bgr | (uintptr_t)pp.out_d8) & 3) == 0 &&
-                         ((uintptr_t)pp.out_m16 & 7) == 0;
         if (vec) {
             if (disp)
                 at(reinterpret_cast<float4*>(disp), i >> 2) =
@@ -1072,7 +1089,7 @@ __global__ __launch_bounds__(256) void k_median_i16(const int16_t* __restrict__ 
             if (pp.mode == POST_NONE) continue;
             PostVals o[4];
 #pragma unroll
-            for (int q = 0; q < 4; ++q) o[q] = post_median(pp, mv[q]);
+            for (int q = 0; q < 4; ++q) o[q] = post(mv[q]);
             at(reinterpret_cast<float4*>(pp.out_a), i >> 2) = make_float4(o[0].a, o[1].a, o[2].a, o[3].a);
             at(reinterpret_cast<uint32_t*>(pp.out_u8), i >> 2) =
                 (uint32_t)o[0].u | ((uint32_t)o[1].u << 8) | ((uint32_t)o[2].u << 16) | ((uint32_t)o[3].u << 24);
@@ -1095,7 +1112,7 @@ __global__ __launch_bounds__(256) void k_median_i16(const int16_t* __restrict__ 
             if (pp.out_m16) at(pp.out_m16, i + q) = (int16_t)mv[q];
             if (pp.out_d8) at(pp.out_d8, i + q) = (uint8_t)((mv[q] >> 4) - pp.d8_base);
             if (pp.mode == POST_NONE) continue;
-            const PostVals o = post_median(pp, mv[q]);
+            const PostVals o = post(mv[q]);
             at(pp.out_a, i + q) = o.a;
             at(pp.out_u8, i + q) = o.u;
             if (pp.mode == POST_SCALED) at(pp.out_b, i + q) = o.b;
@@ -1281,8 +1298,14 @@ int launch_median_i16(const int16_t* in, int H, int W, int row0, int row1, float
         hp.form = (med4 && W >= 256) ? 1 : 0;
         hbx = hp.form ? ((W + 247) / 248 + 3) / 4 : ((W + 59) / 60 + 3) / 4;
     }
+    // unchecked lookups only with the whole-disparity table attached, and only if each of its
+    // planes may be read for the kLutWholeSpan entries a 12-bit index can reach: anything else
+    // takes the checked form
+    const bool wh = pp.lut_unchecked && pp.mode != POST_NONE && pp.lut_shift == 4 && pp.lut_n > 0 &&
+                    pp.lut_cap >= kLutWholeSpan;
     void (*fn)(const int16_t*, int, int, int, int, float*, PostParams, long long, long long, HarrisParams) =
-        hbx == 0 ? k_median_i16<0> : hp.form ? k_median_i16<2> : k_median_i16<1>;
+        wh ? (hbx == 0 ? k_median_i16<0, true> : hp.form ? k_median_i16<2, true> : k_median_i16<1, true>)
+           : (hbx == 0 ? k_median_i16<0, false> : hp.form ? k_median_i16<2, false> : k_median_i16<1, false>);
     hipLaunchKernelGGL(fn, dim3(hp.mbx + hbx, (row1 - row0 + MQ_H - 1) / MQ_H, nf),
                        dim3(256), 0, s, in, H, W, row0, row1, disp, pp, fs_in, fs_out, hp);
     return (int)hipGetLastError();

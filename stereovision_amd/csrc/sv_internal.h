@@ -73,6 +73,11 @@ struct MatchParams {
     // fs_out) as u32, `keys_stride` elements apart; the caller owns them (ring_split_elems)
     uint32_t* keys;
     long long keys_stride;
+    // The columns outside [X0, X1) of rows [row0, row1) of every frame of `out` already hold
+    // the invalid value (minD - 1) * 16 and nothing has written them since: the ring kind then
+    // leaves them alone.  Only a caller that owns `out` and tracks every writer of it may set
+    // this (enqueue_disparity, for the context's own scratch map); the other kinds ignore it.
+    int margins_done;
 };
 
 // Host-side launchers (return hipError_t as int).
@@ -268,7 +273,18 @@ struct PostParams {
     // medians are all multiples of 16 (integer-disparity costs): (D + 1) entries instead of
     // 16 (D + 1), so the epilogue's lookups stay in L1 at large D
     int lut_shift;
+    // Every value of the map is an entry of the whole-disparity table: the map is the output of
+    // an integer matcher (SAD / SSD / HOG: (min_disp + idx) * 16 or the invalid value, and a
+    // median is one of its inputs) enqueued by the same call with this (min_disp, num_disp), and
+    // the table (lut_shift 4) covers [min_disp - 1, min_disp + num_disp).  k_median_i16 then
+    // indexes the table without the range and multiple-of-16 checks or the exact fallback.
+    // Only the call that produced the map sets it; maps from outside keep the checks.  Each of
+    // the three tables must then be readable for kLutWholeSpan entries (attach_lut allocates
+    // the whole-disparity table so): the unchecked index keeps 12 bits.
+    int lut_unchecked;
+    int lut_cap;   // entries each of the three tables may be read for (attach_lut; >= lut_n)
 };
+constexpr int kLutWholeSpan = 4096;   // every int16 x16 value's whole-disparity index, mod 2^12
 // Harris response computed by extra blocks of the median launch (C2): the left gray frames
 // at g (+ z*fs_in bytes, row pitch `pitch`), f32 responses at out (+ z*fs_out floats, row
 // pitch W).  Needs W, H >= 8 (the DPP form).  mbx is set by the launcher.

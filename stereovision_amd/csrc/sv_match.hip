@@ -271,26 +271,44 @@ __device__ __forceinline__ void transpose4(uint32_t a, uint32_t b, uint32_t c, u
 
 // 4-row kind: the pack words of 4 columns from their 2r+4 window rows (one dword = the 4
 // columns of a row, rows y-r .. y+r+3); same layout as build_pack.
+// The common block is 2r-2 rows, so its last word holds four rows or two: two rows take one
+// perm per column straight from the row dwords (selector 0x0c = a zero byte).  The per-row
+// words of outputs 0..3 hold rows {0,1,2}, {1,2,2r+1}, {2,2r+1,2r+2}, {2r+1,2r+2,2r+3}: the
+// row pairs (1,2) and (2r+1,2r+2) that two neighbouring outputs share are interleaved once
+// (2 perms each), and every word is then one perm of a pair against its third row: 24 perms
+// for the four words instead of the 32 of four 3-row transposes.
 template <int R>
 __device__ __forceinline__ void sad4_group_words(const uint32_t (&rw)[2 * R + 4],
                                                  uint32_t (&w)[PackCfg<COST_SAD4, R>::NW][4]) {
     constexpr int NC = PackCfg<COST_SAD4, R>::NW - 4, NCR = 2 * R - 2;
+    static_assert(NCR % 4 == 0 || NCR % 4 == 2, "the common block's last word holds 4 or 2 rows");
 #pragma unroll
     for (int m = 0; m < NC; ++m) {
-        uint32_t d[4];
+        const int b = 3 + 4 * m;
+        if (4 * m + 4 <= NCR) {
+            transpose4(rw[b], rw[b + 1], rw[b + 2], rw[b + 3], w[m]);
+        } else {
 #pragma unroll
-        for (int t = 0; t < 4; ++t) d[t] = 4 * m + t < NCR ? rw[3 + 4 * m + t] : 0u;
-        transpose4(d[0], d[1], d[2], d[3], w[m]);
+            for (int k = 0; k < 4; ++k)   // a_k b_k 0 0
+                w[m][k] = __builtin_amdgcn_perm(rw[b + 1], rw[b], 0x0c0c0400u + 0x0101u * (uint32_t)k);
+        }
     }
+    constexpr int P = 2 * R + 1;
+    const uint32_t pa[2] = {__builtin_amdgcn_perm(rw[2], rw[1], 0x05010400u),    // a0 b0 a1 b1
+                            __builtin_amdgcn_perm(rw[2], rw[1], 0x07030602u)};   // a2 b2 a3 b3
+    const uint32_t pb[2] = {__builtin_amdgcn_perm(rw[P + 1], rw[P], 0x05010400u),
+                            __builtin_amdgcn_perm(rw[P + 1], rw[P], 0x07030602u)};
 #pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        uint32_t d[3];
-        int n = 0;
-#pragma unroll
-        for (int j = q; j <= 2; ++j) d[n++] = rw[j];
-#pragma unroll
-        for (int j = 2 * R + 1; j <= 2 * R + q; ++j) d[n++] = rw[j];
-        transpose4(d[0], d[1], d[2], 0u, w[NC + q]);
+    for (int k = 0; k < 4; ++k) {
+        // column k's pair sits in bytes 2(k&1), 2(k&1)+1 of the pair word k >> 1 (selector 4..7:
+        // the first operand); its third row is byte k of the second operand
+        const uint32_t p0 = 4u + 2u * (k & 1), p1 = p0 + 1u, s = (uint32_t)k;
+        const uint32_t row_pair = 0x0c000000u | (p1 << 16) | (p0 << 8) | s;   // row, pair
+        const uint32_t pair_row = 0x0c000000u | (s << 16) | (p1 << 8) | p0;   // pair, row
+        w[NC + 0][k] = __builtin_amdgcn_perm(pa[k >> 1], rw[0], row_pair);
+        w[NC + 1][k] = __builtin_amdgcn_perm(pa[k >> 1], rw[P], pair_row);
+        w[NC + 2][k] = __builtin_amdgcn_perm(pb[k >> 1], rw[2], row_pair);
+        w[NC + 3][k] = __builtin_amdgcn_perm(pb[k >> 1], rw[P + 2], pair_row);
     }
 }
 
@@ -391,6 +409,13 @@ __device__ __forceinline__ void build_all_packs(const MatchParams& a, int y, int
 // wave waits for its global loads once per MF groups instead of once per group (the
 // per-group form left ~8% of k_match's time in the segment prologue).  Groups touching the
 // image border load nothing and take build_pack afterwards.
+// An interior group stores all of its four columns, also those just outside the wave's range
+// (indices -3 .. -1 and n .. n + 2), so the regions need unused slots around them: RING_PAD_F
+// in front of the left region, RING_PAD_M between the two (the left's 3 rear slots and the
+// right's 4 front slots, index -3 sitting in slot -4, are the same ones: both only ever receive
+// unread columns) and RING_PAD_B behind the right one.
+constexpr int RING_PAD_F = 3, RING_PAD_M = 4, RING_PAD_B = 3;
+constexpr int RING_PAD = RING_PAD_F + RING_PAD_M + RING_PAD_B;
 template <int R, int MF, int DPL>
 __device__ __forceinline__ void build_ring_packs(const MatchParams& a, int y, int cL0, int NL, int cR0,
                                                  int NRlog, int c0, PackOut<COST_SAD4, R> Lp,
@@ -417,6 +442,7 @@ __device__ __forceinline__ void build_ring_packs(const MatchParams& a, int y, in
     int roff[NRW];                                           // row offsets (wave-uniform)
 #pragma unroll
     for (int j = 0; j < NRW; ++j) roff[j] = clampi(y - R + j, 0, a.H - 1) * a.pitch;
+    static_assert(DPL == 4, "a 4-column group meets one slot gap at a wave-uniform column");
     for (int g0 = 0; g0 < G; g0 += 64 * MF) {
         uint32_t rw[MF][NRW];
 #pragma unroll
@@ -443,16 +469,29 @@ __device__ __forceinline__ void build_ring_packs(const MatchParams& a, int y, in
             const int cfirst = right ? cR0 : cL0, n = right ? NRlog : NL;
             const PackOut<COST_SAD4, R> base = right ? Rp : Lp;
             if (cg >= 0 && cg + 4 <= a.W) {
+                // All four columns, with no range test per column: the up to three columns of a
+                // region's first or last group that lie outside [cfirst, cfirst + n) land in
+                // the pad slots around the regions, which nothing reads.  Left: consecutive
+                // slots from one base.  Right: group j's column k has index 4j + d + k, so its
+                // slot is (d + 5j) + k + floor((d + k + c0) / 4): one base per lane and four
+                // wave-uniform offsets (d = aR - cR0 is the same for every group of the wave).
                 uint32_t w[NW][4];
                 sad4_group_words<R>(rw[m], w);
-#pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    const int idx = cg + k - cfirst;
-                    if (idx < 0 || idx >= n) continue;
+                auto store = [&](const PackOut<COST_SAD4, R> gb, int k, int slot) {
                     uint32_t v[8];
 #pragma unroll
                     for (int i = 0; i < 8; ++i) v[i] = i < NW ? w[i < NW ? i : 0][k] : 0u;
-                    put<COST_SAD4, R>(base + (right ? rslot(idx, c0, DPL) : idx), v);
+                    put<COST_SAD4, R>(gb + slot, v);
+                };
+                if (right) {
+                    const int d = aR - cR0;                  // -3 .. 0
+                    const PackOut<COST_SAD4, R> gb = Rp + (d + ((cg - aR) >> 2) * (DPL + 1));
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) store(gb, k, k + ((d + k + c0 + DPL) >> 2) - 1);   // (floor)
+                } else {
+                    const PackOut<COST_SAD4, R> gb = Lp + (cg - cL0);
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) store(gb, k, k);
                 }
             } else {
 #pragma unroll
@@ -947,9 +986,10 @@ __global__ __launch_bounds__(64, 2) void k_match_ring(MatchParams a) {
     constexpr int c0 = 1;                               // chunk starts (index = 3 mod 4) meet slot gaps
     const int NRphys = NRlog + (NRlog + c0) / RG_DPL + 1;
     uint4* wbase = smem + (LDSMIN ? RING_SCRATCH_BYTES / 16 : 0);   // the packs follow the scratch
-    typename P::CT* cbase = reinterpret_cast<typename P::CT*>(wbase + (size_t)(NL + NRphys));
-    const PackOut<COST_SAD4, R> Lw{wbase, cbase};
-    const PackOut<COST_SAD4, R> Rw{wbase + NL, cbase + NL};
+    // (pad slots around the two regions: build_ring_packs)
+    typename P::CT* cbase = reinterpret_cast<typename P::CT*>(wbase + (size_t)(NL + NRphys + RING_PAD));
+    const PackOut<COST_SAD4, R> Lw{wbase + RING_PAD_F, cbase + RING_PAD_F};
+    const PackOut<COST_SAD4, R> Rw{wbase + NL + RING_PAD_F + RING_PAD_M, cbase + NL + RING_PAD_F + RING_PAD_M};
     const PackPtr<COST_SAD4, R> Lp{Lw.x, Lw.c};
     const PackPtr<COST_SAD4, R> Rp{Rw.x, Rw.c};
 
@@ -960,7 +1000,9 @@ __global__ __launch_bounds__(64, 2) void k_match_ring(MatchParams a) {
     const int cR0 = cL0 - a.minD - (4 * LPG - 1);       // R index i -> column cR0 + i
     build_ring_packs<R, 3, RG_DPL>(a, yc, cL0, NL, cR0, NRlog, c0, Lw, Rw, lane);
 
-    if (!KEYS && bx == 0) {  // columns outside the matched band are invalid
+    // columns outside the matched band are invalid (margins_done: an earlier launch into the
+    // same map left them so, see MatchParams)
+    if (!KEYS && bx == 0 && !a.margins_done) {
         const int16_t inv = (int16_t)((a.minD - 1) * 16);
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
@@ -1443,7 +1485,7 @@ size_t ring_lds_bytes(int lpg, int seg, int r, bool ldsmin) {
     const int tn = (seg + 2 * r + 3) & ~3;
     const int nl = wc - seg + tn + 1, nr = wc - seg + tn + 4 * lpg;
     const int nrp = nr + (nr + 1) / RG_DPL + 1;
-    return (size_t)(nl + nrp) * (r <= 3 ? 20 : r <= 5 ? 24 : 28) + (ldsmin ? RING_SCRATCH_BYTES : 0);
+    return (size_t)(nl + nrp + RING_PAD) * (r <= 3 ? 20 : r <= 5 ? 24 : 28) + (ldsmin ? RING_SCRATCH_BYTES : 0);
 }
 
 template <int R, int LPG, bool KEYS, bool SSD>
