@@ -221,8 +221,6 @@ int enqueue_disparity(sv_ctx* c, const uint8_t* L, const uint8_t* R, int H, int 
     a.pad_key = (uint32_t)((sv::max_cost(win, cost) + 1) << plan.dbits);
     a.out = out;
     a.opitch = opitch;
-    SV_HIP(c->wctr.ensure_zeroed(256));
-    a.work_ctr = c->wctr.as<unsigned>();
     a.nf = nf < 1 ? 1 : nf;
     a.fs_in = fs_in;
     a.fs_out = fs_out;
@@ -567,7 +565,7 @@ void sv_destroy(sv_ctx* c) {
         (void)hipStreamSynchronize(c->stream);
         c->prof_drain();
         for (auto e : c->pool) (void)hipEventDestroy(e);
-        DevBuf* bufs[] = {&c->wctr, &c->img[0], &c->img[1], &c->gray[0], &c->gray[1], &c->d16, &c->fa, &c->fb,
+        DevBuf* bufs[] = {&c->img[0], &c->img[1], &c->gray[0], &c->gray[1], &c->d16, &c->fa, &c->fb,
                           &c->fc, &c->u8, &c->harris, &c->hog[0], &c->hog[1], &c->fin, &c->lut,
                           &c->rmap1, &c->rmap2, &c->rdst[0], &c->rdst[1], &c->stats, &c->sel,
                           &c->sg_hsum, &c->sg_c, &c->sg_l, &c->sg_lt, &c->sg_band, &c->cc_parent,

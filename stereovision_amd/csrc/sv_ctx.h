@@ -114,7 +114,6 @@ struct sv_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
     std::mutex mu;
-    DevBuf wctr;   // persistent matcher's work counters (zeroed once; the kernel resets them)
     DevBuf img[2], gray[2], d16, fa, fb, fc, u8, harris, hog[2], fin, lut, rmap1, rmap2, rdst[2], stats, sel,
         sg_hsum, sg_c, sg_l, sg_lt, sg_band, sg_rec, cc_parent, cc_size, hist_copies, cmap, bgr;
     uint8_t cmap_host[768] = {};   // BGR table currently in `cmap`

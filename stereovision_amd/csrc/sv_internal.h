@@ -63,12 +63,12 @@ struct MatchParams {
     int nf;
     long long fs_in, fs_out, fs_hist;
     uint32_t pad_key;      // (max_cost + 1) << dbits: key offset of padding disparities
-    int segm;              // segment length in LPG units (set by launch_match)
-    // persistent kinds: the launching context's work counters (16 B, zero between launches;
-    // the kernel's last wave resets them), so concurrent launches on other contexts never
-    // share one
-    unsigned* work_ctr;
-    int xcd_map;           // ring kind: XCD-aware tile order (launch_ring_rl)
+    // set by the launchers.  k_match: segment length per lane group in units of LPG columns;
+    // k_match_ring: segment width per lane group in columns (sv_match_packs.h)
+    int segm;
+    // ring kind: XCD-aware tile order (launch_ring_rl).  16-byte aligned: the fields from here
+    // on keep the argument-block offsets that the ring kernels' scalar loads were measured with
+    alignas(16) int xcd_map;
     // split ring (SAD, 256 < D <= 512): two argmin-key planes laid out like `out` (opitch,
     // fs_out) as u32, `keys_stride` elements apart; the caller owns them (ring_split_elems)
     uint32_t* keys;

@@ -1,7 +1,7 @@
 """GPU parity of the ring matcher's and the median kernel's work outside their inner loops,
 bit-exact against the C oracle:
 
-  * the pack build (sv_match.hip sad4_group_words: the per-row words of a 4-column group are
+  * the pack build (sv_match_packs.h sad4_group_words: the per-row words of a 4-column group are
     built from two shared row pairs) for every radius that shares it, on aligned sources (the
     buffer row loads of build_ring_packs), on unaligned ones (build_all_packs' per-column
     form), with clamped top and bottom rows, partial last segments, widths that are no multiple
@@ -160,7 +160,7 @@ def check_batch(res, maps, mode, min_disp, D):
             np.testing.assert_array_equal(res["d16"][z], d16, err_msg=f"int16 map, frame {z}")
 
 
-# ---- ring_seg / ring_lds_bytes of sv_match.hip, to find the widths that give two segments ----
+# ---- ring_seg / ring_lds_bytes of sv_match_ring.hip, to find the widths that give two segments ----
 def _ring_lds(lpg, seg, r):
     wc = (64 // lpg) * seg
     tn = (seg + 2 * r + 3) & ~3

@@ -660,12 +660,20 @@ def test_registered_outputs_dma_path_matches_host_expansion(engine, scaled):
         engine._noreg = noreg
 
 
-@pytest.mark.parametrize("win,D", [(9, 128), (15, 256)])
+@pytest.mark.parametrize("win,D", [(9, 128), (15, 256), (5, 64), (7, 160), (11, 128)])
 def test_ring_kind_huge_out_pitch_falls_back_exactly(engine, win, D):
     """the ring kernel's 32-bit buffer offsets cannot address an int16 map whose
-    rows lie past 2^31 bytes; such maps take the size_t-addressed four-row kind, bit-exact."""
-    H, W = 40, 400
-    opitch = (1 << 26) + 64                       # 2 * 40 * 2^26 bytes = 5.4 GB of map span
+    rows lie past 2^31 bytes; such maps take the size_t-addressed four-row kind, bit-exact.
+    The last three cases are that kind's other forms on the smallest shape that still falls
+    back (2 * ((H + 3) * opitch + W + 64) >= 2^31) with a partial last block of four rows: win 5
+    the 4-byte common slot and the 16-key reduce-scatter, (7, 160) 6 disparities x 32 lanes
+    and the batched row reduction of 16-bit keys, win 11 the 8-byte common slot at r 5."""
+    if (win, D) in ((9, 128), (15, 256)):
+        H, W = 40, 400
+        opitch = (1 << 26) + 64                   # 2 * 40 * 2^26 bytes = 5.4 GB of map span
+    else:
+        H, W = 6, D + 100
+        opitch = (1 << 27) + 64                   # 2 * 5 * 2^27 bytes = 1.3 GB of map span
     L, R, _ = stereo_pair(H, W, D, seed=31)
     exp = O.disparity16(L, R, 0, D, win)
     dL, dR = engine.dev_alloc(H * W), engine.dev_alloc(H * W)
@@ -676,7 +684,7 @@ def test_ring_kind_huge_out_pitch_falls_back_exactly(engine, win, D):
     try:
         engine.disparity_dev(dL, dR, H, W, W, 0, D, win, "sad", 0, H, d16, opitch)
         engine.synchronize()
-        for y in (0, 1, H // 2, H - 2, H - 1):
+        for y in sorted({0, 1, H // 2, H - 2, H - 1}):
             row = engine.to_host(d16 + 2 * y * opitch, (W,), np.int16)
             np.testing.assert_array_equal(row, exp[y], err_msg=f"row {y}")
     finally:

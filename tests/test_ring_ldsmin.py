@@ -1,4 +1,4 @@
-"""GPU parity of the ring kind's LDS argmin fold (sv_match.hip k_match_ring LDSMIN: 32-lane
+"""GPU parity of the ring kind's LDS argmin fold (sv_match_ring.hip k_match_ring LDSMIN: 32-lane
 groups at win 9, i.e. 64 < D <= 128; every lane stores its 8 keys of a step pair to a per-wave
 LDS scratch, lane r folds key r >> 3 of group (r >> 2) & 1) against the C oracle's
 winner-take-all (first minimum), bit-exact.

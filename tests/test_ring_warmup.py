@@ -1,4 +1,4 @@
-"""GPU parity of the ring kind's warm-up (sv_match.hip k_match_ring: the first 2r steps of a
+"""GPU parity of the ring kind's warm-up (sv_match_ring.hip k_match_ring: the first 2r steps of a
 segment run as add-only chunks ahead of the loop, the cost ring starts unwritten and the last
 warm-up chunk zeroes the few slots read before they are written) and of build_ring_packs' row
 loads, against the C oracle's winner-take-all (first minimum), bit-exact.

@@ -1,6 +1,6 @@
 """GPU parity of the split ring kind: SAD windows with 256 < D <= 512 (the reference's own
 default NUM_DISP = 16*20 = 320 with WINDOW_SIZE = 7, depth_map.py:31-33) run the ring kind
-twice (d < 256 and d >= 256) into argmin-key planes and merge them (sv_match.hip
+twice (d < 256 and d >= 256) into argmin-key planes and merge them (sv_match_ring.hip
 ring_split / k_merge_ring_keys), against the C oracle's winner-take-all (first minimum)."""
 import numpy as np
 import pytest

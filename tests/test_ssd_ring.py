@@ -1,4 +1,4 @@
-"""GPU parity of the ring kind's SSD form (win 5..9, D <= 256: sv_match.hip ring_ssd): the SAD
+"""GPU parity of the ring kind's SSD form (win 5..9, D <= 256: sv_match_ring.hip ring_ssd): the SAD
 ring's packs and cost ring with Σ(L-R)² = ΣL² + ΣR² - 2ΣLR per window column, against the C
 oracle's SSD winner-take-all (first minimum); north_star's "SAD/SSD over a disparity sweep"."""
 import numpy as np
