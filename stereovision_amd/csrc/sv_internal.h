@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <cstdlib>
 #include <string>
 
 struct sv_comm;
@@ -17,6 +18,27 @@ namespace sv {
 // is split into several ops inside large bodies, so inline asm (plain VOP3: no hazards).
 __device__ __forceinline__ void sad_u32_acc(uint32_t& a, uint32_t b, uint32_t c) {
     asm("v_sad_u32 %0, %0, %1, %2" : "+v"(a) : "v"(b), "v"(c));
+}
+
+__device__ __forceinline__ int clampi(int v, int lo, int hi) { return min(max(v, lo), hi); }
+
+// cv2.cvtColor(BGR2GRAY), 14-bit fixed point (depth_map.py:871-880)
+__device__ __forceinline__ int bgr_to_gray(int b, int g, int r) {
+    return (b * 1868 + g * 9617 + r * 4899 + (1 << 13)) >> 14;
+}
+
+// ---- environment switches (A/B measurements): callers keep the value in a function-local
+// static, so each is read once per process -----------------------------------------------
+// default on: off with NAME=0; default off: on with NAME=1
+inline bool env_flag(const char* name, bool default_on) {
+    const char* e = std::getenv(name);
+    return default_on ? !(e && e[0] == '0') : (e && e[0] == '1');
+}
+// the integer value of NAME when it lies in [lo, hi], else 0 (unset, unparsable, out of range)
+inline int env_int(const char* name, int lo, int hi) {
+    const char* e = std::getenv(name);
+    const int v = e ? std::atoi(e) : 0;
+    return v >= lo && v <= hi ? v : 0;
 }
 
 // Sets the calling thread's sv_last_error() message; returns `code`.

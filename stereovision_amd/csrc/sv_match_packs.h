@@ -15,22 +15,6 @@ constexpr int COST_SAD4 = 4;          // internal kind: SAD, four output rows pe
 // Kind actually launched for a public cost: SAD with win >= 5 runs four rows per wave.
 inline int kind_of(int cost, int win) { return cost == COST_SAD && win >= 5 ? COST_SAD4 : cost; }
 
-// ---- environment switches (A/B measurements): callers keep the value in a function-local
-// static, so each is read once per process -----------------------------------------------
-// default on: off with NAME=0; default off: on with NAME=1
-inline bool env_flag(const char* name, bool default_on) {
-    const char* e = std::getenv(name);
-    return default_on ? !(e && e[0] == '0') : (e && e[0] == '1');
-}
-// the integer value of NAME when it lies in [lo, hi], else 0 (unset, unparsable, out of range)
-inline int env_int(const char* name, int lo, int hi) {
-    const char* e = std::getenv(name);
-    const int v = e ? std::atoi(e) : 0;
-    return v >= lo && v <= hi ? v : 0;
-}
-
-__device__ __forceinline__ int clampi(int v, int lo, int hi) { return min(max(v, lo), hi); }
-
 // ---- pack shape --------------------------------------------------------------------------
 // A column pack holds `nw` live dwords.  `nd` is the kind's width parameter: byte dwords (SAD,
 // SSD), unused (HOG), the window radius r (SAD4: ceil((2r-2)/4) common dwords + 4 per-row

@@ -9,6 +9,8 @@
 //                     (depth_map.py:815-826, fused_depth_map.py:480-491), u8 gray or BGR,
 //                     optionally fused with cvtColor(BGR2GRAY) so the rectified gray image
 //                     the matcher reads is written directly (rectify -> gray in one pass).
+//  * k_gray           cv2.cvtColor(BGR2GRAY) alone, for frames that arrive rectified
+//                     (depth_map.py:871-880).
 //
 // k_remap is HBM-bound: per output pixel it reads the 6-byte map entry once, 4 source taps
 // (mostly L2 hits: neighbouring output pixels read neighbouring source pixels) and writes
@@ -22,6 +24,15 @@
 
 namespace sv {
 namespace {
+
+__global__ void k_gray(const uint8_t* __restrict__ bgr, int H, int W, int pitch,
+                       uint8_t* __restrict__ gray) {
+    const int x = blockIdx.x * blockDim.x + threadIdx.x;
+    const int y = blockIdx.y;
+    if (x >= W) return;
+    const uint8_t* p = bgr + (size_t)y * pitch + 3 * x;
+    gray[(size_t)y * W + x] = (uint8_t)bgr_to_gray(p[0], p[1], p[2]);
+}
 
 __device__ __forceinline__ int cv_round_i32(double v) {
     // saturate_cast<int>(double) on x86: round half to even; NaN / out of range -> INT_MIN
@@ -159,8 +170,7 @@ __global__ __launch_bounds__(256) void k_remap(RemapArgs a) {
             outv[0] |= (uint32_t)((acc[0] + 512) >> 10) << (8 * k);
         } else if (GRAY) {
             const int b = (acc[0] + 512) >> 10, g = (acc[1] + 512) >> 10, r = (acc[2] + 512) >> 10;
-            const int gy = (b * 1868 + g * 9617 + r * 4899 + (1 << 13)) >> 14;
-            outv[0] |= (uint32_t)gy << (8 * k);
+            outv[0] |= (uint32_t)bgr_to_gray(b, g, r) << (8 * k);
         } else {
 #pragma unroll
             for (int c = 0; c < 3; ++c) {
@@ -257,6 +267,11 @@ __global__ __launch_bounds__(256) void k_resize_linear(ResizeArgs a) {
 }
 
 }  // namespace
+
+int launch_gray(const uint8_t* bgr, int H, int W, int pitch, uint8_t* gray, hipStream_t s) {
+    hipLaunchKernelGGL(k_gray, dim3((W + 255) / 256, H), dim3(256), 0, s, bgr, H, W, pitch, gray);
+    return (int)hipGetLastError();
+}
 
 int launch_resize_linear(const void* src, int sH, int sW, int cn, int spitch, long long sfs, void* dst,
                          int dH, int dW, int dpitch, long long dfs, int nf, bool f32, hipStream_t s) {

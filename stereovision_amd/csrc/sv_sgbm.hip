@@ -67,13 +67,6 @@ __device__ __forceinline__ uint32_t row_min_u(uint32_t v) {
     v = min(v, (uint32_t)dpp_ror<1>((int)v));
     return v;
 }
-__device__ __forceinline__ int row_max(int v) {
-    v = max(v, dpp_ror<8>(v));
-    v = max(v, dpp_ror<4>(v));
-    v = max(v, dpp_ror<2>(v));
-    v = max(v, dpp_ror<1>(v));
-    return v;
-}
 
 // -------------------------------------------------------------------------------------
 // pixel cost + horizontal window sums
@@ -286,9 +279,6 @@ typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ uint32_t pk_add16(uint32_t a, uint32_t b) {   // v_pk_add_u16 (mod 2^16)
     return __builtin_bit_cast(uint32_t, __builtin_bit_cast(u16x2, a) + __builtin_bit_cast(u16x2, b));
 }
-__device__ __forceinline__ uint32_t pk_sub16(uint32_t a, uint32_t b) {   // v_pk_sub_u16 (mod 2^16)
-    return __builtin_bit_cast(uint32_t, __builtin_bit_cast(u16x2, a) - __builtin_bit_cast(u16x2, b));
-}
 
 // Per-pixel {value, BT lo, BT hi} records of both images (k_sgbm_cost stages rows of them)
 __global__ __launch_bounds__(256) void k_sgbm_records(SgbmArgs a) {
@@ -480,14 +470,6 @@ template <int LPC> __device__ __forceinline__ uint32_t line_min_u(uint32_t v) {
     if constexpr (LPC == 32) {
         const RowPair p = row_pair((int)v);
         v = min((uint32_t)p.even, (uint32_t)p.odd);
-    }
-    return v;
-}
-template <int LPC> __device__ __forceinline__ int line_max(int v) {
-    v = row_max(v);
-    if constexpr (LPC == 32) {
-        const RowPair p = row_pair(v);
-        v = max(p.even, p.odd);
     }
     return v;
 }

@@ -53,7 +53,7 @@ __device__ __forceinline__ void hist_add(uint32_t* h, uint32_t bin) {
 constexpr int kSlots = (kTile * kTile / 4 + 63) / 64;   // 9
 
 __device__ __forceinline__ uint32_t gray_at(const uint8_t* p, int cn) {
-    return cn == 3 ? (uint32_t)((p[0] * 1868 + p[1] * 9617 + p[2] * 4899 + (1 << 13)) >> 14) : (uint32_t)p[0];
+    return cn == 3 ? (uint32_t)bgr_to_gray(p[0], p[1], p[2]) : (uint32_t)p[0];
 }
 
 template <int AGG>

@@ -777,6 +777,45 @@ def test_harris_dpp_kernel_equals_lds_kernel():
         assert np.abs(got - O.harris(g)).max() <= HARRIS_TOL, (H, W)
 
 
+def test_hog_tile_kernel_equals_column_run_kernel():
+    """k_hog_hist<r> (the 64x16 tile form: records over 2 GB, SV_HOG_STRIP=0) gives the same
+    bytes as k_hog_hist_cr<r, 4> (the default), each in a child, at every radius 0..7: a 1-pixel
+    image (reflect-101 of size 1, window wider than the image), a window taller than the image,
+    exactly one tile, a second tile row of one row with a column short of a tile, three tile
+    rows with two columns into a third tile column, and one column past the column-run wave's
+    256; and both equal the oracle exactly."""
+    import os
+    import subprocess
+    import sys
+    cases = [(H, W, win) for H, W in [(1, 1), (2, 70), (16, 64), (17, 63), (33, 130), (9, 257)]
+             for win in range(1, 16, 2)]
+    code = ("import sys, numpy as np; sys.path.insert(0, %r)\n"
+            "from stereovision_amd.engine import get_engine\n"
+            "e = get_engine(0)\n"
+            "for H, W, win in %r:\n"
+            "    g = np.random.default_rng(H * 1000 + W + win).integers(0, 256, (H, W), dtype=np.uint8)\n"
+            "    g[:, ::7] = 255\n"
+            "    sys.stdout.buffer.write(e.hog_hist(g, win).tobytes())\n") % (
+        os.path.dirname(os.path.dirname(os.path.abspath(__file__))), cases)
+    outs = []
+    for strip in ("1", "0"):   # column runs, 64x16 tiles
+        r = subprocess.run([sys.executable, "-c", code], capture_output=True, timeout=120,
+                           env=dict(os.environ, SV_HOG_STRIP=strip, SV_WARMUP_AT_IMPORT="0"))
+        assert r.returncode == 0, r.stderr.decode()[-2000:]
+        outs.append(r.stdout)
+    assert outs[0] == outs[1]
+    off = 0
+    for H, W, win in cases:
+        g = np.random.default_rng(H * 1000 + W + win).integers(0, 256, (H, W), dtype=np.uint8)
+        g[:, ::7] = 255
+        exp = O.hog_hist(g, win)
+        for k, out in enumerate(outs):
+            got = np.frombuffer(out[off:off + exp.nbytes], np.uint16).reshape(exp.shape)
+            np.testing.assert_array_equal(got, exp, err_msg=f"SV_HOG_STRIP={1 - k} {(H, W, win)}")
+        off += exp.nbytes
+    assert off == len(outs[0])
+
+
 class _LocalGather:
     """A process group standing in for `world` ranks of one process: gatherv at the root copies
     every other rank's block (from that rank's RowTiledDepthMap buffer) into the root's."""
