@@ -31,6 +31,12 @@
  *   sv_select_count/ranks            order statistics of np.percentile in
  *                                    calibrate_midas_to_stereo / normalize_to_stereo_range
  *                                    (fused_depth_map.py:1169-1257, 1503-1554)
+ *   sv_gauss_blur_f32_dev            cv2.GaussianBlur(x, (k, k), 0) on a float32 map
+ *                                    (fused_depth_map.py:1638)
+ *   sv_bilateral_f32_dev             cv2.bilateralFilter on a float32 map
+ *                                    (fused_depth_map.py:1688, :2769, :1403-1411), optionally with
+ *                                    the clip / uint8 / colormap / range block (:1696-1708)
+ *   sv_fuse_blend_dev                the blend of fuse_depth_maps (fused_depth_map.py:1603-1684)
  *   sv_multi_gpu_batch               the per-frame create_depth_map loop, frame-sharded over
  *                                    several devices from one process
  *   sv_rectify_pair                  the two remap calls of apply_stereo_rectification
@@ -93,7 +99,8 @@ enum sv_kernel {
     SV_K_SCATTER = 15,  /* multi-GPU input scatters (row bands + halos), per context stream */
     SV_K_H2D = 16,      /* host-buffer entry points: the frame pair's upload (per image) */
     SV_K_D2H = 17,      /* host-buffer entry points: the outputs' download */
-    SV_NKERNELS = 18
+    SV_K_FUSE = 18,     /* fuse_depth_maps: the blend, the Gaussian and the bilateral filter */
+    SV_NKERNELS = 19
 };
 
 int sv_version(void);
@@ -490,6 +497,62 @@ int sv_select_ranks_batch(sv_ctx* ctx, const float* d_x, int64_t n, int64_t x_st
  * mode 1: out = float32(float64(x) * ds + doff); mode 2: out = fc. */
 int sv_affine_f32_dev(sv_ctx* ctx, const float* d_x, int64_t n, int mode, float fa, float fb,
                       float fc, float fd, double ds, double doff, float* d_out, void* stream);
+
+/* ---- fuse_depth_maps (fused_depth_map.py:1560-1718) and its two float32 filters ----------
+ * Maps are float32 HxW, dense, finite; borders BORDER_REFLECT_101.  Every exp of the filters is
+ * evaluated by the caller in float64 and passed as float32 tables (fusion.py: gaussian_kernel,
+ * bilateral_tables), so the kernels' results are bit-identical to a NumPy restatement of the
+ * same arithmetic (parity with a particular OpenCV build is unpinned).  All three
+ * return SV_EINVAL before anything is enqueued for a null pointer, an unsupported ksize or
+ * radius, or H or W <= the filter radius. */
+
+/* cv2.GaussianBlur(x, (ksize, ksize), 0) (:1638): ksize odd in [3, 31], coef = the ksize
+ * normalised coefficients (host), rows first with a float32 intermediate, each pass
+ * s = c0 x0; s = s + c_i (x_-i + x_+i), i = 1..ksize/2.  d_dst != d_src. */
+int sv_gauss_blur_f32_dev(sv_ctx* ctx, const float* d_src, int H, int W, const float* coef, int ksize,
+                          float* d_dst, void* stream);
+
+/* cv2.bilateralFilter(x, d, sigma_color, sigma_space) on one float32 channel (:1688, :2769,
+ * :1403-1411) with the tables built by the caller: radius in [1, 7]; space_w (host) = one weight
+ * per tap of the radius-r disc without its centre, dy outer and dx inner; lut (host) = the 4098
+ * entries of the colour table over 4096 bins; scale = bins per unit of |difference|.  radius 0:
+ * no filter (the copy path of a constant map, or the max <= 10 branch of :1687), the outputs
+ * are formed from d_src elementwise.  Outputs, each optional: d_dst_f32 = the filter's output;
+ * d_dst_u8 = np.clip(out, 0, 255).astype(uint8) (:1696-1697); d_dst_bgr = cmap_bgr[d_dst_u8]
+ * (HxWx3; cmap_bgr: host, 256 x 3 BGR bytes; :1700); minmax_out (host) = min and max of the
+ * clipped map (:1708) — the call then waits for the result.  With radius > 0 the call waits
+ * once for the upload of the colour table (the caller's tables may go when it returns); the
+ * filter itself is only enqueued. */
+int sv_bilateral_f32_dev(sv_ctx* ctx, const float* d_src, int H, int W, int radius, const float* space_w,
+                         const float* lut, float scale, float* d_dst_f32, uint8_t* d_dst_u8,
+                         uint8_t* d_dst_bgr, const uint8_t* cmap_bgr, float* minmax_out, void* stream);
+
+/* The blend of fuse_depth_maps (:1603-1684) in one launch.  base 0: stereo * stereo_weight
+ * with conf (NULL: ones), 1: midas, 2: flow.  midas_fill (base 0): fw = clip(GaussianBlur((1 -
+ * conf) * midas_fill_weight, ksize), 0, 1); where conf < conf_threshold and fw > 0.1:
+ * fused = fused * (1 - fw) + midas * fw.  flow_fill (base 0 or 1): where fused <
+ * hole_threshold or fused == 0: fused = fused * flow_k1 + flow * flow_k2 (k1 = float32(1 -
+ * weight), k2 = float32(weight)).  coef / ksize as for sv_gauss_blur_f32_dev (midas_fill). */
+typedef struct sv_fuse_args {
+    const float* d_stereo;
+    const float* d_conf;
+    const float* d_midas;
+    const float* d_flow;
+    int H, W;
+    int base;
+    int midas_fill, flow_fill;
+    float stereo_weight, midas_fill_weight, conf_threshold, hole_threshold, flow_k1, flow_k2;
+    const float* coef;   /* host */
+    int ksize;
+} sv_fuse_args;
+/* range of the blended map and the pixels each fill changed (the np.any guards of :1645, :1656) */
+typedef struct sv_fuse_stats {
+    float min, max;
+    int64_t n_midas, n_hole;
+} sv_fuse_stats;
+/* stats (host, nullable): the call then waits for the result. */
+int sv_fuse_blend_dev(sv_ctx* ctx, const sv_fuse_args* args, float* d_fused, sv_fuse_stats* stats,
+                      void* stream);
 
 /* cv2.resize(x, (dW, dH), INTER_LINEAR) of a float32 HxW map (calibrate_midas_to_stereo,
  * fused_depth_map.py:1216-1217): OpenCV's float path, S0*b0 + S1*b1 without contraction.

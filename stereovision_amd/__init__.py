@@ -6,6 +6,17 @@ through a C ABI (``include/stereovision_amd.h``, ``lib/libsvhip.so``).  See DESI
 """
 from .engine import (COSTS, Engine, EngineUnavailable, SVError, device_count, get_engine,
                      load_library, plan)
+from .fusion import (bilateral_filter, bilateral_filter_dev, bilateral_tables, fuse_maps,
+                     fuse_maps_dev, gaussian_blur, gaussian_kernel)
 
 __all__ = ["COSTS", "Engine", "EngineUnavailable", "SVError", "device_count", "get_engine",
-           "load_library", "plan"]
+           "load_library", "plan", "bilateral_filter", "bilateral_filter_dev", "bilateral_tables",
+           "fuse_maps", "fuse_maps_dev", "gaussian_blur", "gaussian_kernel", "fuse_depth_maps"]
+
+
+def __getattr__(name):
+    # fused_depth_map starts the engine warm-up when it is imported: only on first use
+    if name == "fuse_depth_maps":
+        from .fused_depth_map import fuse_depth_maps
+        return fuse_depth_maps
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -63,8 +63,10 @@ def apply(u8: np.ndarray, name: str) -> np.ndarray:
     return _LUTS[name][u8]
 
 
-def put_text(img: np.ndarray, text: str, org=(10, 30)) -> np.ndarray:
-    """cv2.putText(img, text, org, FONT_HERSHEY_COMPLEX, 0.7, white, 2) when cv2 exists."""
+def put_text(img: np.ndarray, text: str, org=(10, 30), scale: float = 0.7, color=(255, 255, 255),
+             thickness: int = 2) -> np.ndarray:
+    """cv2.putText(img, text, org, FONT_HERSHEY_COMPLEX, scale, color, thickness) when cv2
+    exists (defaults: 0.7, white, 2)."""
     if cv2 is not None:
-        cv2.putText(img, text, org, cv2.FONT_HERSHEY_COMPLEX, 0.7, (255, 255, 255), 2)
+        cv2.putText(img, text, org, cv2.FONT_HERSHEY_COMPLEX, scale, color, thickness)
     return img

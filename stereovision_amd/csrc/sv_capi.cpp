@@ -570,7 +570,7 @@ void sv_destroy(sv_ctx* c) {
                           &c->rmap1, &c->rmap2, &c->rdst[0], &c->rdst[1], &c->stats, &c->sel,
                           &c->sg_hsum, &c->sg_c, &c->sg_l, &c->sg_lt, &c->sg_band, &c->cc_parent,
                           &c->hist_copies, &c->cmap, &c->bgr, &c->m16,
-                          &c->cc_size, &c->sg_rec, &c->gm16, &c->keys, &c->lutw};
+                          &c->cc_size, &c->sg_rec, &c->gm16, &c->keys, &c->lutw, &c->fuse};
         if (c->lut_ev) (void)hipEventDestroy(c->lut_ev);
         if (c->lutw_ev) (void)hipEventDestroy(c->lutw_ev);
         if (c->scr_ev) (void)hipEventDestroy(c->scr_ev);

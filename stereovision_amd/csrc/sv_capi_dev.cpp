@@ -1153,6 +1153,142 @@ int sv_affine_f32_dev(sv_ctx* c, const float* d_x, int64_t n, int mode, float fa
     return 0;
 }
 
+// ---------------------------------------------------------------- fuse_depth_maps
+// c->fuse: the launch's accumulator copies, then the bilateral colour table
+constexpr size_t kFuseLutOff = sv::kFuseStatsBytes;
+constexpr size_t kFuseBytes = kFuseLutOff + sv::kBilateralLut * sizeof(float);
+
+// ksize odd in [3, 31] and the map larger than the radius; fills c[0..r] centre first
+static int gauss_coef(const float* coef, int ksize, int H, int W, float* c) {
+    if (ksize < 3 || ksize > 31 || ksize % 2 == 0) return fail(SV_EINVAL, "Gaussian ksize must be odd in [3, 31]");
+    if (!coef) return fail(SV_EINVAL, "null Gaussian coefficients");
+    const int r = ksize / 2;
+    if (H <= r || W <= r) return fail(SV_EINVAL, "map not larger than the Gaussian radius (H, W > ksize / 2)");
+    for (int i = 0; i < 16; ++i) c[i] = i <= r ? coef[r + i] : 0.f;
+    return 0;
+}
+
+int sv_gauss_blur_f32_dev(sv_ctx* c, const float* d_src, int H, int W, const float* coef, int ksize, float* d_dst,
+                          void* stream) {
+    SV_ENTER(c);
+    if (!d_src || !d_dst || d_src == d_dst || H <= 0 || W <= 0) return fail(SV_EINVAL, "bad Gaussian blur arguments");
+    sv::GaussArgs a{};
+    int rc = gauss_coef(coef, ksize, H, W, a.c);
+    if (rc) return rc;
+    a.src = d_src;
+    a.dst = d_dst;
+    a.H = H;
+    a.W = W;
+    a.r = ksize / 2;
+    hipStream_t s = pick(c, stream);
+    SV_LAUNCH(c, SV_K_FUSE, s, sv::launch_gauss_f32(a, s));
+    return 0;
+}
+
+int sv_bilateral_f32_dev(sv_ctx* c, const float* d_src, int H, int W, int radius, const float* space_w,
+                         const float* lut, float scale, float* d_dst_f32, uint8_t* d_dst_u8, uint8_t* d_dst_bgr,
+                         const uint8_t* cmap_bgr, float* minmax_out, void* stream) {
+    SV_ENTER(c);
+    if (!d_src || H <= 0 || W <= 0) return fail(SV_EINVAL, "bad bilateral filter arguments");
+    if (radius < 0 || radius > sv::kBilateralMaxR) return fail(SV_EINVAL, "bilateral radius must be in [0, 7]");
+    if (radius > 0 && (!space_w || !lut)) return fail(SV_EINVAL, "null bilateral tables");
+    if (radius > 0 && (H <= radius || W <= radius))
+        return fail(SV_EINVAL, "map not larger than the bilateral radius (H, W > radius)");
+    if (!d_dst_f32 && !d_dst_u8 && !d_dst_bgr && !minmax_out) return fail(SV_EINVAL, "no bilateral output");
+    if (d_dst_f32 == d_src) return fail(SV_EINVAL, "bilateral filter in place");
+    if (d_dst_bgr && !cmap_bgr) return fail(SV_EINVAL, "colormap output without a table");
+    hipStream_t s = pick(c, stream);
+    SV_SCRATCH(c, s);
+    SV_HIP(c->fuse.ensure(kFuseBytes));
+    sv::BilateralArgs a{};
+    a.src = d_src;
+    a.H = H;
+    a.W = W;
+    a.r = radius;
+    a.scale = scale;
+    a.dst_f32 = d_dst_f32;
+    a.dst_u8 = d_dst_u8;
+    if (d_dst_bgr) {
+        sv::PostParams pp{};
+        int rc = attach_cmap(c, pp, cmap_bgr, d_dst_bgr, s);
+        if (rc) return rc;
+        a.dst_bgr = pp.out_bgr;
+        a.cmap = pp.cmap;
+    }
+    if (d_dst_u8 || d_dst_bgr || minmax_out) {
+        a.stats = c->fuse.as<uint32_t>();
+        SV_HIP(hipMemsetAsync(a.stats, 0, sv::kFuseStatsBytes, s));
+    }
+    if (radius > 0) {
+        float* d_lut = reinterpret_cast<float*>(c->fuse.as<char>() + kFuseLutOff);
+        SV_HIP(hipMemcpyAsync(d_lut, lut, sv::kBilateralLut * sizeof(float), hipMemcpyHostToDevice, s));
+        SV_HIP(hipStreamSynchronize(s));   // the caller's table may go once this call returns
+        a.lut = d_lut;
+    }
+    SV_LAUNCH(c, SV_K_FUSE, s, sv::launch_bilateral_f32(a, space_w, s));
+    if (minmax_out) {
+        uint32_t slots[sv::kFuseSlots * sv::kFuseSlotStride], w[4];
+        SV_HIP(hipMemcpyAsync(slots, a.stats, sizeof(slots), hipMemcpyDeviceToHost, s));
+        SV_HIP(hipStreamSynchronize(s));
+        sv::fuse_stats_fold(slots, w);
+        minmax_out[0] = sv::fuse_stat_min(w);
+        minmax_out[1] = sv::fuse_stat_max(w);
+    }
+    return 0;
+}
+
+int sv_fuse_blend_dev(sv_ctx* c, const sv_fuse_args* g, float* d_fused, sv_fuse_stats* stats, void* stream) {
+    SV_ENTER(c);
+    if (!g || !d_fused) return fail(SV_EINVAL, "null fuse arguments");
+    if (g->H <= 0 || g->W <= 0) return fail(SV_EINVAL, "bad fuse map size");
+    if (g->base < 0 || g->base > 2) return fail(SV_EINVAL, "fuse base must be 0 (stereo), 1 (midas) or 2 (flow)");
+    const bool mfill = g->midas_fill != 0, ffill = g->flow_fill != 0;
+    if (mfill && g->base != sv::FUSE_BASE_STEREO) return fail(SV_EINVAL, "midas fill needs the stereo base");
+    if (ffill && g->base == sv::FUSE_BASE_FLOW) return fail(SV_EINVAL, "flow fill on the flow base");
+    if ((g->base == sv::FUSE_BASE_STEREO && !g->d_stereo) || ((g->base == sv::FUSE_BASE_MIDAS || mfill) && !g->d_midas) ||
+        ((g->base == sv::FUSE_BASE_FLOW || ffill) && !g->d_flow))
+        return fail(SV_EINVAL, "null fuse input map");
+    sv::FuseBlendArgs a{};
+    if (mfill) {
+        int rc = gauss_coef(g->coef, g->ksize, g->H, g->W, a.c);
+        if (rc) return rc;
+        a.r = g->ksize / 2;
+    }
+    hipStream_t s = pick(c, stream);
+    SV_SCRATCH(c, s);
+    SV_HIP(c->fuse.ensure(kFuseBytes));
+    a.stereo = g->d_stereo;
+    a.conf = g->d_conf;
+    a.midas = g->d_midas;
+    a.flow = g->d_flow;
+    a.fused = d_fused;
+    a.stats = c->fuse.as<uint32_t>();
+    a.H = g->H;
+    a.W = g->W;
+    a.base = g->base;
+    a.midas_fill = mfill;
+    a.flow_fill = ffill;
+    a.sw = g->stereo_weight;
+    a.mfw = g->midas_fill_weight;
+    a.thr = g->conf_threshold;
+    a.hthr = g->hole_threshold;
+    a.k1 = g->flow_k1;
+    a.k2 = g->flow_k2;
+    SV_HIP(hipMemsetAsync(a.stats, 0, sv::kFuseStatsBytes, s));
+    SV_LAUNCH(c, SV_K_FUSE, s, sv::launch_fuse_blend(a, s));
+    if (stats) {
+        uint32_t slots[sv::kFuseSlots * sv::kFuseSlotStride], w[4];
+        SV_HIP(hipMemcpyAsync(slots, a.stats, sizeof(slots), hipMemcpyDeviceToHost, s));
+        SV_HIP(hipStreamSynchronize(s));
+        sv::fuse_stats_fold(slots, w);
+        stats->min = sv::fuse_stat_min(w);
+        stats->max = sv::fuse_stat_max(w);
+        stats->n_midas = w[2];
+        stats->n_hole = w[3];
+    }
+    return 0;
+}
+
 // ---------------------------------------------------------------- SGBM-3WAY mode
 int sv_sgbm_dev(sv_ctx* c, const uint8_t* d_left, const uint8_t* d_right, int H, int W, int pitch, int min_disp,
                 int num_disp, int block_size, int P1, int P2, int disp12_max_diff, int pre_filter_cap,

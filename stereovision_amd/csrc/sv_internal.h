@@ -203,6 +203,73 @@ struct AffineArgs {
 };
 int launch_affine_f32(const AffineArgs& a, hipStream_t s);
 
+// fuse_depth_maps and its filters (sv_fuse.hip; fused_depth_map.py:1560-1718).
+struct GaussArgs {
+    const float* src;
+    float* dst;               // != src
+    int H, W, r;              // r = ksize / 2 in [1, 15]; H, W > r
+    float c[16];              // c[0] the centre coefficient, c[i] the one at distance i
+};
+enum FuseBase { FUSE_BASE_STEREO = 0, FUSE_BASE_MIDAS = 1, FUSE_BASE_FLOW = 2 };
+struct FuseBlendArgs {
+    const float* stereo;
+    const float* conf;        // nullable: ones
+    const float* midas;
+    const float* flow;
+    float* fused;
+    uint32_t* stats;          // kFuseStatsBytes of accumulators, zero on entry (fuse_stats_fold)
+    int H, W, base;
+    int midas_fill, flow_fill;
+    int r;                    // Gaussian radius of the fill weight (midas_fill)
+    float sw, mfw, thr, hthr, k1, k2;
+    float c[16];
+};
+constexpr int kBilateralMaxR = 7;
+constexpr int kBilateralMaxTaps = 148;    // lattice points of the radius-7 disc, less the centre
+constexpr int kBilateralLut = 4096 + 2;   // colour-table entries
+struct BilateralArgs {
+    const float* src;
+    const float* lut;         // device, kBilateralLut entries (r > 0)
+    float* dst_f32;           // nullable: the filter's output
+    uint8_t* dst_u8;          // nullable: clip(out, 0, 255) truncated (needs stats)
+    uint8_t* dst_bgr;         // nullable: cmap[dst_u8] as B, G, R bytes (needs stats)
+    const uint32_t* cmap;     // 256 entries B | G << 8 | R << 16
+    uint32_t* stats;          // nullable: kFuseStatsBytes of accumulators of the clipped map's range, zero on entry
+    int H, W, r, ntaps;       // r = 0: no filter, the outputs elementwise; ntaps, sw, off: set by the launcher
+    float scale;
+    float sw[kBilateralMaxTaps];
+    short off[kBilateralMaxTaps];
+};
+// the taps of radius r in the filter's order (dy outer, dx inner, the disc without its centre)
+int bilateral_taps(int r, int* dy, int* dx);
+int launch_gauss_f32(const GaussArgs& a, hipStream_t s);
+int launch_fuse_blend(const FuseBlendArgs& a, hipStream_t s);
+// space_w: host, one weight per tap
+int launch_bilateral_f32(BilateralArgs a, const float* space_w, hipStream_t s);
+// The accumulators (`stats`) of a launch: kFuseSlots copies of 4 words, kFuseSlotStride words
+// apart, zero on entry; block b adds into copy b % kFuseSlots.  fuse_stats_fold merges the
+// copies of a finished launch; words [0] and [1] then decode to the map's minimum and maximum.
+constexpr int kFuseSlots = 32, kFuseSlotStride = 32;
+constexpr size_t kFuseStatsBytes = (size_t)kFuseSlots * kFuseSlotStride * sizeof(uint32_t);
+inline void fuse_stats_fold(const uint32_t* slots, uint32_t w[4]) {
+    w[0] = w[1] = w[2] = w[3] = 0;
+    for (int s = 0; s < kFuseSlots; ++s) {
+        const uint32_t* p = slots + s * kFuseSlotStride;
+        w[0] = p[0] > w[0] ? p[0] : w[0];
+        w[1] = p[1] > w[1] ? p[1] : w[1];
+        w[2] += p[2];
+        w[3] += p[3];
+    }
+}
+inline float fuse_stat_decode(uint32_t k) {
+    const uint32_t u = (k & 0x80000000u) ? (k ^ 0x80000000u) : ~k;
+    float f;
+    __builtin_memcpy(&f, &u, sizeof f);
+    return f;
+}
+inline float fuse_stat_min(const uint32_t* w) { return fuse_stat_decode(~w[0]); }
+inline float fuse_stat_max(const uint32_t* w) { return fuse_stat_decode(w[1]); }
+
 // SGBM-3WAY mode (sv_sgbm.hip).
 struct SgbmArgs {
     const uint8_t* L;

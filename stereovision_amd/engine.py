@@ -25,7 +25,7 @@ COSTS = {"sad": 0, "ssd": 1, "hog": 2, "sgbm": 3}
 POST_NONE, POST_DEPTH, POST_SCALED = 0, 1, 2
 KERNELS = {"gray": 0, "harris": 1, "hog": 2, "match": 3, "median": 4, "post": 5, "remap": 6,
            "undistort": 7, "resize": 8, "stats": 9, "select": 10, "affine": 11, "sgbm": 12,
-           "speckle": 13, "gather": 14, "scatter": 15, "h2d": 16, "d2h": 17}
+           "speckle": 13, "gather": 14, "scatter": 15, "h2d": 16, "d2h": 17, "fuse": 18}
 
 # Every symbol include/stereovision_amd.h declares (checked by tests/test_capi.py).
 EXPORTED = [
@@ -46,7 +46,8 @@ EXPORTED = [
     "sv_multi_gpu_dev", "sv_depth_map_color", "sv_stereo_scaled_color", "sv_profile_region_begin",
     "sv_profile_region_end", "sv_comm_scatterv", "sv_band_rows_in", "sv_release_scratch",
     "sv_frame_stats_batch_dev", "sv_select_count_batch", "sv_select_ranks_batch", "sv_event_record",
-    "sv_stream_wait_event", "sv_post_m16_dev",
+    "sv_stream_wait_event", "sv_post_m16_dev", "sv_gauss_blur_f32_dev", "sv_bilateral_f32_dev",
+    "sv_fuse_blend_dev",
 ]
 BAND_MARGIN = 8   # SV_BAND_MARGIN: spare rows around a band-only input buffer
 COMM_ID_BYTES = 128
@@ -127,6 +128,21 @@ class MapOut(ctypes.Structure):
                 ("depth_range", _c_float), ("min_disp_global", _c_float), ("disparity", _vp),
                 ("out_a", _vp), ("out_u8", _vp), ("out_b", _vp), ("med16", _vp), ("d8", _vp),
                 ("cmap_bgr", _vp), ("bgr", _vp), ("harris", _vp)]
+
+
+class FuseArgs(ctypes.Structure):
+    """sv_fuse_args: the inputs of one sv_fuse_blend_dev launch."""
+    _fields_ = [("d_stereo", _vp), ("d_conf", _vp), ("d_midas", _vp), ("d_flow", _vp),
+                ("H", _c_int), ("W", _c_int), ("base", _c_int), ("midas_fill", _c_int),
+                ("flow_fill", _c_int), ("stereo_weight", _c_float), ("midas_fill_weight", _c_float),
+                ("conf_threshold", _c_float), ("hole_threshold", _c_float), ("flow_k1", _c_float),
+                ("flow_k2", _c_float), ("coef", _vp), ("ksize", _c_int)]
+
+
+class FuseStats(ctypes.Structure):
+    """sv_fuse_stats."""
+    _fields_ = [("min", _c_float), ("max", _c_float), ("n_midas", ctypes.c_int64),
+                ("n_hole", ctypes.c_int64)]
 
 
 def map_out(mode: int = POST_NONE, disparity: int = 0, out_a: int = 0, out_u8: int = 0, out_b: int = 0,
@@ -230,6 +246,10 @@ def _declare(lib):
                                    ctypes.c_int64, _c_float, _i64p, _c_int, _f32p], _c_int),
         "sv_affine_f32_dev": ([_vp, _vp, ctypes.c_int64, _c_int, _c_float, _c_float, _c_float, _c_float,
                                ctypes.c_double, ctypes.c_double, _vp, _vp], _c_int),
+        "sv_gauss_blur_f32_dev": ([_vp, _vp, _c_int, _c_int, _f32p, _c_int, _vp, _vp], _c_int),
+        "sv_bilateral_f32_dev": ([_vp, _vp, _c_int, _c_int, _c_int, _NullableF32, _NullableF32, _c_float,
+                                  _vp, _vp, _vp, _NullableU8, _NullableF32, _vp], _c_int),
+        "sv_fuse_blend_dev": ([_vp, ctypes.POINTER(FuseArgs), _vp, ctypes.POINTER(FuseStats), _vp], _c_int),
         "sv_sgbm": ([_vp, _u8p, _u8p] + [_c_int] * 14 + [_i16p], _c_int),
         "sv_sgbm_dev": ([_vp, _vp, _vp] + [_c_int] * 13 + [_vp, _c_int, _vp], _c_int),
         "sv_filter_speckles": ([_vp, _i16p] + [_c_int] * 5, _c_int),
@@ -327,6 +347,12 @@ def _cost(cost) -> int:
         except KeyError:
             raise ValueError(f"unknown cost {cost!r}; expected one of {sorted(COSTS)}") from None
     return int(cost)
+
+
+def bilateral_tap_count(radius: int) -> int:
+    """Taps of sv_bilateral_f32_dev for `radius`: the lattice points of the disc, less the centre."""
+    r = int(radius)
+    return sum(1 for y in range(-r, r + 1) for x in range(-r, r + 1) if 0 < y * y + x * x <= r * r)
 
 
 def _image(a: np.ndarray) -> tuple[np.ndarray, int, int, int]:
@@ -1024,6 +1050,68 @@ class Engine:
         _check("sv_affine_f32_dev", self.lib.sv_affine_f32_dev(
             self._h, d_x, int(n), int(mode), np.float32(fa), np.float32(fb), np.float32(fc),
             np.float32(fd), float(ds), float(doff), d_out, stream or None))
+
+    # -- fuse_depth_maps and its filters (fusion.py builds the tables) ------------------------
+    def gauss_blur_f32_dev(self, d_src: int, H: int, W: int, coef: np.ndarray, d_dst: int, stream: int = 0):
+        """cv2.GaussianBlur(x, (k, k), 0) of a float32 device map; coef = the k coefficients."""
+        coef = np.ascontiguousarray(coef, np.float32)
+        _check("sv_gauss_blur_f32_dev", self.lib.sv_gauss_blur_f32_dev(
+            self._h, d_src, int(H), int(W), coef, int(coef.size), d_dst, stream or None))
+
+    def bilateral_f32_dev(self, d_src: int, H: int, W: int, radius: int, space_w, lut, scale: float,
+                          d_dst_f32: int = 0, d_dst_u8: int = 0, d_dst_bgr: int = 0, cmap=None,
+                          minmax: bool = False, stream: int = 0):
+        """cv2.bilateralFilter of a float32 device map with host-built tables (radius 0: no
+        filter), and optionally the clip / uint8 / colormap outputs; minmax: returns the
+        (min, max) of the clipped map after waiting for it."""
+        radius = int(radius)
+        if radius > 0:
+            space_w = np.ascontiguousarray(space_w, np.float32)
+            lut = np.ascontiguousarray(lut, np.float32)
+            if lut.size != 4098:
+                raise ValueError(f"bilateral colour table: 4098 entries expected, got {lut.size}")
+            if 0 < radius <= 7 and space_w.size != bilateral_tap_count(radius):
+                raise ValueError(f"bilateral space weights: {bilateral_tap_count(radius)} taps expected "
+                                 f"for radius {radius}, got {space_w.size}")
+        else:
+            space_w = lut = None
+        if cmap is not None:
+            cmap = np.ascontiguousarray(cmap, np.uint8)
+            if cmap.shape != (256, 3):
+                raise ValueError("colormap table must be 256 x 3")
+        mm = np.zeros(2, np.float32) if minmax else None
+        _check("sv_bilateral_f32_dev", self.lib.sv_bilateral_f32_dev(
+            self._h, d_src, int(H), int(W), radius, space_w, lut, np.float32(scale), d_dst_f32 or None,
+            d_dst_u8 or None, d_dst_bgr or None, cmap, mm, stream or None))
+        return (mm[0], mm[1]) if minmax else None
+
+    def fuse_blend_dev(self, d_fused: int, H: int, W: int, base: int, d_stereo: int = 0, d_conf: int = 0,
+                       d_midas: int = 0, d_flow: int = 0, midas_fill: bool = False, flow_fill: bool = False,
+                       stereo_weight=1.0, midas_fill_weight=0.0, conf_threshold=0.0, hole_threshold=0.0,
+                       flow_k1=1.0, flow_k2=0.0, coef=None, stats: bool = True, stream: int = 0):
+        """The blend of fuse_depth_maps (sv_fuse_blend_dev); stats: waits and returns
+        {"min", "max", "n_midas", "n_hole"} of the blended map."""
+        a = FuseArgs()
+        a.d_stereo, a.d_conf, a.d_midas, a.d_flow = d_stereo or None, d_conf or None, d_midas or None, d_flow or None
+        a.H, a.W, a.base = int(H), int(W), int(base)
+        a.midas_fill, a.flow_fill = int(bool(midas_fill)), int(bool(flow_fill))
+        a.stereo_weight = np.float32(stereo_weight)
+        a.midas_fill_weight = np.float32(midas_fill_weight)
+        a.conf_threshold = np.float32(conf_threshold)
+        a.hole_threshold = np.float32(hole_threshold)
+        a.flow_k1 = np.float32(flow_k1)
+        a.flow_k2 = np.float32(flow_k2)
+        if coef is not None:
+            coef = np.ascontiguousarray(coef, np.float32)
+            a.coef = coef.ctypes.data
+            a.ksize = int(coef.size)
+        st = FuseStats()
+        _check("sv_fuse_blend_dev", self.lib.sv_fuse_blend_dev(
+            self._h, ctypes.byref(a), d_fused, ctypes.byref(st) if stats else None, stream or None))
+        if not stats:
+            return None
+        return {"min": np.float32(st.min), "max": np.float32(st.max), "n_midas": int(st.n_midas),
+                "n_hole": int(st.n_hole)}
 
     def rectify_pair(self, dmaps, left, right):
         """Both remaps of apply_stereo_rectification with device-resident maps

@@ -10,7 +10,12 @@ with the print-traceback-zeros error convention (:1031-1041).  The numeric body 
 one pass of the gfx950 kernels (``sv_stereo_scaled``).  The scaled-parameter rules of the
 caller (fused_depth_map.py:2258-2266) are exposed as :func:`scaled_stereo_params`.
 
-The reference calls this function from a ThreadPoolExecutor worker and waits at most
+``fuse_depth_maps(...)`` (fused_depth_map.py:1560-1718) keeps its name, arguments, module
+settings (``FUSION_*``, ``fusion_params``, read at call time) and return value as well; its
+blend, Gaussian fill weight, bilateral filter, quantisation and colormap run on the GPU
+(``fusion.fuse_maps``).
+
+The reference calls the stereo function from a ThreadPoolExecutor worker and waits at most
 0.5 s (fused_depth_map.py:2591-2598, :2671); :func:`warmup` builds the engine and runs
 the scaled path once at the processing size, so the first real frame does not pay HIP
 initialisation, context creation, code-object loading and staging allocation inside that
@@ -25,6 +30,7 @@ import traceback
 import numpy as np
 
 from . import colormap
+from . import fusion as _fusion
 from . import rectify as _rectify
 from .fusion import (calibrate_midas_to_stereo, detect_camera_occlusion,  # noqa: F401
                      normalize_to_stereo_range)
@@ -38,6 +44,20 @@ MIN_DISP_BASE = 0
 NUM_DISP_BASE = 16 * 20
 WINDOW_SIZE_BASE = 7
 COST = "sad"
+
+# fuse_depth_maps' settings (fused_depth_map.py:81-116), read at call time
+FUSION_WEIGHTS = {"stereo_base": 0.8, "midas_max_fill": 0.9, "flow_max_fill": 0.5}
+FUSION_THRESHOLDS = {"stereo_low_conf": 0.5, "midas_fill_start": 0.3, "flow_hole_threshold": 15,
+                     "flow_min_inliers": 15}
+FUSION_SMOOTHING = {"midas_blend_radius": 15, "fusion_bilateral_d": 9, "fusion_bilateral_sigma": 75}
+FUSION_METHODS = {"use_stereo": True, "use_midas_fill": True, "use_flow_fill": True}
+fusion_params = {
+    "stereo_weight": FUSION_WEIGHTS["stereo_base"],
+    "midas_fill_weight": FUSION_WEIGHTS["midas_max_fill"],
+    "flow_fill_weight": FUSION_WEIGHTS["flow_max_fill"],
+    "stereo_conf_threshold": FUSION_THRESHOLDS["stereo_low_conf"],
+    "flow_hole_threshold": FUSION_THRESHOLDS["flow_hole_threshold"],
+}
 
 
 def scaled_stereo_params(processing_scale: float = None, num_disp_base: int = None,
@@ -87,6 +107,67 @@ def create_depth_map_stereo_scaled(left_img, right_img, min_disp, num_disp, wind
         empty = np.zeros((h, w), dtype=np.float32)
         empty_colormap = colormap.apply(np.zeros((h, w), dtype=np.uint8), "jet")
         return empty, empty.copy(), empty_colormap, empty.copy()
+
+
+last_fuse_info = None   # fusion.fuse_maps' info of the last fuse_depth_maps call + mode_parts, mode_text
+
+
+def _valid(use, m) -> bool:
+    return bool(use) and m is not None and np.size(m) > 0
+
+
+def fuse_depth_maps(stereo_depth, stereo_conf, midas_depth_calibrated, midas_conf,
+                    flow_depth_normalized, camera_moving, use_stereo=True, use_midas=True,
+                    use_flow=True):
+    """fused_depth_map.py:1560-1718 on the MI355X engine: (fused_uint8, fused_colormap), or
+    None when no method is valid.  The blend, the Gaussian fill weight, the bilateral filter,
+    the quantisation and the colormap run in two kernel launches (fusion.fuse_maps);
+    ``last_fuse_info`` keeps the mode parts and the range of the last call."""
+    global last_fuse_info
+    valid_stereo = _valid(use_stereo, stereo_depth)
+    valid_midas = _valid(use_midas, midas_depth_calibrated)
+    valid_flow = _valid(use_flow, flow_depth_normalized) and bool(camera_moving)
+    if not (valid_stereo or valid_midas or valid_flow):
+        return None
+    fp = fusion_params
+    res = _fusion.fuse_maps(
+        stereo_depth if valid_stereo else None,
+        stereo_conf if valid_stereo else None,
+        midas_depth_calibrated if valid_midas else None,
+        flow_depth_normalized if valid_flow else None,
+        cmap=colormap.table("jet"), engine=get_engine(),
+        stereo_weight=fp["stereo_weight"], midas_fill_weight=fp["midas_fill_weight"],
+        flow_fill_weight=fp["flow_fill_weight"], stereo_conf_threshold=fp["stereo_conf_threshold"],
+        flow_hole_threshold=fp["flow_hole_threshold"], use_midas_fill=FUSION_METHODS["use_midas_fill"],
+        use_flow_fill=FUSION_METHODS["use_flow_fill"], midas_blend_radius=FUSION_SMOOTHING["midas_blend_radius"],
+        bilateral_d=FUSION_SMOOTHING["fusion_bilateral_d"],
+        bilateral_sigma=FUSION_SMOOTHING["fusion_bilateral_sigma"])
+    fused_uint8, fused_colormap, info = res
+    # the mode parts (:1629, :1650, :1662, :1668, :1678, :1684): a fill is named when it changed a pixel
+    mode_parts = []
+    if info["base"] == _fusion.BASE_STEREO:
+        mode_parts.append(f"Stereo\u00d7{fp['stereo_weight']:.1f}")
+        if info["n_midas"] > 0:
+            mode_parts.append(f"MiDaS_fill\u00d7{fp['midas_fill_weight']:.1f}")
+    elif info["base"] == _fusion.BASE_MIDAS:
+        mode_parts.append("MiDaS_base")
+    else:
+        mode_parts.append("Flow_base")
+    if info["n_hole"] > 0:
+        mode_parts.append(f"Flow_fill\u00d7{fp['flow_fill_weight']:.1f}")
+    mode_text = " + ".join(mode_parts) if mode_parts else "NO DATA"
+    min_val, max_val = info["range"]
+    info = dict(info, mode_parts=mode_parts, mode_text=mode_text)
+    last_fuse_info = info
+    w = fused_uint8.shape[1]
+    colormap.put_text(fused_colormap, f"FUSED: {mode_text}", (10, 30), scale=0.65)
+    colormap.put_text(fused_colormap, f"Range: {min_val:.0f}-{max_val:.0f}", (10, 55), scale=0.5,
+                      color=(0, 255, 255), thickness=1)
+    if valid_flow:     # (camera_moving holds whenever the flow map is valid)
+        motion_text = "CAM MOVING" if camera_moving else "STATIC"
+        colormap.put_text(fused_colormap, motion_text, (w - 150, 30), scale=0.5,
+                          color=(0, 255, 0) if camera_moving else (0, 0, 255), thickness=1)
+    return fused_uint8, fused_colormap
 
 
 def warmup(height: int = 356, width: int = 633, processing_scale: float = None) -> None:

@@ -4,7 +4,10 @@ Drop-ins for fused_depth_map.py's
   detect_camera_occlusion(left, right, occlusion_threshold=0.45)          :131-301
   calibrate_midas_to_stereo(midas_depth, stereo_disparity, stereo_conf)   :1169-1257
   normalize_to_stereo_range(depth_map, stereo_disparity)                  :1503-1554
-with the reference's arguments, return values and decisions.
+with the reference's arguments, return values and decisions, and the numeric body of
+  fuse_depth_maps(stereo, conf, midas, midas_conf, flow, camera_moving, ...)   :1560-1718
+(``fuse_maps`` / ``fuse_maps_dev``; the drop-in itself is fused_depth_map.fuse_depth_maps)
+with the two filters it is built on, ``gaussian_blur`` and ``bilateral_filter``.
 
 * The occlusion statistics come from one ``k_frame_stats`` launch per pair: exact integer
   moments of every 48x48 block and the 256-bin histogram of each image.  np.mean and the
@@ -19,6 +22,10 @@ with the reference's arguments, return values and decisions.
   the 'linear' method (scalar q on float32 -> float32 arithmetic, a list of q -> float64),
   so results are bit-identical to np.percentile.
 * The elementwise epilogues run in ``k_affine_f32`` with the reference's precision.
+* fuse_depth_maps runs in two launches (``k_fuse_blend``, ``k_bilateral_f32``) around one host
+  step: the blended map's range comes back, ``bilateral_tables`` builds the colour table with
+  NumPy in float64 and uploads it.  The kernels call no exp of their own, which is what makes
+  the maps bit-identical to a NumPy restatement (OpenCV parity is unpinned).
 
 Inputs are host NumPy arrays (as in the reference); ``*_dev`` variants take device
 pointers for pipelines that keep the maps in HBM.
@@ -245,6 +252,196 @@ def calibrate_midas_to_stereo(midas_depth, stereo_disparity, stereo_confidence):
         scale = (stereo_max - stereo_min) / (midas_max - midas_min + 1e-8)
     offset = stereo_min - midas_min * scale
     return _affine(eng, d_md, (H, W), AFF_F64, ds=float(scale), doff=float(offset))
+
+
+# ----------------------------------------------------------------------------------------
+# fuse_depth_maps and its filters   :1560-1718
+# ----------------------------------------------------------------------------------------
+BILATERAL_BINS = 4096          # colour-table bins; the table holds BILATERAL_BINS + 2 entries
+BILATERAL_MAX_RADIUS = 7
+FLT_EPSILON = float(np.finfo(np.float32).eps)
+BASE_STEREO, BASE_MIDAS, BASE_FLOW = 0, 1, 2
+
+
+def gaussian_kernel(ksize: int) -> np.ndarray:
+    """The ksize float32 coefficients of cv2.GaussianBlur(x, (ksize, ksize), 0): sigma =
+    0.3 ((ksize - 1) / 2 - 1) + 0.8, exp in float64, normalised by the float64 sum of the
+    float32 values."""
+    ksize = int(ksize)
+    if ksize < 3 or ksize > 31 or ksize % 2 == 0:
+        raise ValueError(f"gaussian_kernel: ksize must be odd in [3, 31], got {ksize}")
+    sigma = 0.3 * ((ksize - 1) * 0.5 - 1) + 0.8
+    scale2x = -0.5 / (sigma * sigma)
+    x = np.arange(ksize, dtype=np.float64) - (ksize - 1) * 0.5
+    g = np.exp(scale2x * (x * x)).astype(np.float32)
+    total = 0.0
+    for v in g:                       # in index order: the sum is part of the definition
+        total += float(v)
+    return (g.astype(np.float64) * (1.0 / total)).astype(np.float32)
+
+
+def bilateral_radius(d: int, sigma_space: float) -> int:
+    if sigma_space <= 0:
+        sigma_space = 1
+    r = int(d) // 2 if d > 0 else int(round(1.5 * sigma_space))
+    return max(r, 1)
+
+
+def bilateral_tables(mn, mx, d: int, sigma_color: float, sigma_space: float):
+    """Host tables of cv2.bilateralFilter on a float32 map whose values span [mn, mx]:
+    (radius, space weights float32 [taps], colour table float32 [4098], scale float32).
+    Taps: dy outer, dx inner over [-r, r], without the centre and the corners outside the
+    disc.  Table entry i = exp((i / scale)^2 * (-0.5 / sigma_color^2)) until the first entry
+    that rounds to zero, zeros after it."""
+    if sigma_color <= 0:
+        sigma_color = 1
+    if sigma_space <= 0:
+        sigma_space = 1
+    r = bilateral_radius(d, sigma_space)
+    if r > BILATERAL_MAX_RADIUS:
+        raise ValueError(f"bilateral_tables: radius {r} > {BILATERAL_MAX_RADIUS} is not supported")
+    gs = -0.5 / (float(sigma_space) * float(sigma_space))
+    gc = -0.5 / (float(sigma_color) * float(sigma_color))
+    r2 = np.array([dy * dy + dx * dx for dy in range(-r, r + 1) for dx in range(-r, r + 1)
+                   if (dy or dx) and math.sqrt(dy * dy + dx * dx) <= r], np.float64)
+    sw = np.exp(r2 * gs).astype(np.float32)
+    length = np.float32(float(mx) - float(mn))
+    scale = np.float32(BILATERAL_BINS) / length
+    v = np.arange(BILATERAL_BINS + 2, dtype=np.float64) / float(scale)
+    lut = np.exp(v * v * gc).astype(np.float32)
+    zero = np.flatnonzero(lut == 0)
+    if zero.size:                     # (monotone, so already so: stated for the contract)
+        lut[zero[0]:] = 0
+    return r, sw, lut, scale
+
+
+def _check_maps(name, maps):
+    """float32 (TypeError) maps of one 2-D shape (ValueError); None entries are skipped."""
+    out, shape = [], None
+    for label, m in maps:
+        if m is None:
+            out.append(None)
+            continue
+        m = _f32_map(m, f"{name}: {label}")
+        if m.ndim != 2:
+            raise ValueError(f"{name}: {label} must be HxW, got shape {m.shape}")
+        if shape is None:
+            shape = m.shape
+        elif m.shape != shape:
+            raise ValueError(f"{name}: {label} has shape {m.shape}, expected {shape}")
+        out.append(m)
+    return out, shape
+
+
+def gaussian_blur(src, ksize: int, engine=None) -> np.ndarray:
+    """cv2.GaussianBlur(src, (ksize, ksize), 0) of a float32 HxW host map, on the GPU."""
+    (src,), (H, W) = _check_maps("gaussian_blur", [("src", src)])
+    coef = gaussian_kernel(ksize)
+    if H <= ksize // 2 or W <= ksize // 2:
+        raise ValueError(f"gaussian_blur: map {H}x{W} not larger than the radius {ksize // 2}")
+    eng = engine or get_engine()
+    d_src = eng.upload("gb_src", src)
+    d_dst = eng.scratch("gb_dst", src.nbytes)
+    eng.gauss_blur_f32_dev(d_src, H, W, coef, d_dst)
+    return eng.to_host(d_dst, (H, W), np.float32)
+
+
+def bilateral_filter_dev(eng, d_src: int, H: int, W: int, mn, mx, d: int, sigma_color: float,
+                         sigma_space: float, d_dst: int, stream: int = 0) -> None:
+    """cv2.bilateralFilter of a float32 device map whose minimum and maximum are mn, mx
+    (they size the colour table), into d_dst (!= d_src)."""
+    if abs(float(mx) - float(mn)) < FLT_EPSILON:          # a constant map: a copy
+        eng.bilateral_f32_dev(d_src, H, W, 0, None, None, 0.0, d_dst_f32=d_dst, stream=stream)
+        return
+    r, sw, lut, scale = bilateral_tables(mn, mx, d, sigma_color, sigma_space)
+    if H <= r or W <= r:
+        raise ValueError(f"bilateral_filter: map {H}x{W} not larger than the radius {r}")
+    eng.bilateral_f32_dev(d_src, H, W, r, sw, lut, scale, d_dst_f32=d_dst, stream=stream)
+
+
+def bilateral_filter(src, d: int, sigma_color: float, sigma_space: float, engine=None) -> np.ndarray:
+    """cv2.bilateralFilter(src, d, sigma_color, sigma_space) of a float32 HxW host map, on the
+    GPU (the range of src, an exact reduction, is taken here)."""
+    (src,), (H, W) = _check_maps("bilateral_filter", [("src", src)])
+    eng = engine or get_engine()
+    d_src = eng.upload("bf_src", src)
+    d_dst = eng.scratch("bf_dst", src.nbytes)
+    bilateral_filter_dev(eng, d_src, H, W, src.min(), src.max(), d, sigma_color, sigma_space, d_dst)
+    return eng.to_host(d_dst, (H, W), np.float32)
+
+
+FUSE_DEFAULTS = dict(stereo_weight=0.8, midas_fill_weight=0.9, flow_fill_weight=0.5,
+                     stereo_conf_threshold=0.5, flow_hole_threshold=15, use_midas_fill=True,
+                     use_flow_fill=True, midas_blend_radius=15, bilateral_d=9, bilateral_sigma=75)
+
+
+def fuse_maps_dev(eng, H: int, W: int, d_stereo: int, d_conf: int, d_midas: int, d_flow: int,
+                  d_fused: int, d_u8: int, d_bgr: int = 0, cmap=None, stream: int = 0, **params) -> dict:
+    """The numeric body of fuse_depth_maps (:1603-1700) on float32 device maps (0 = the map is
+    absent or not valid): blend -> d_fused (float32 scratch), then the bilateral filter when
+    max(fused) > 10, clip, uint8 -> d_u8 and the colormap -> d_bgr (optional).  One host
+    round trip in between (the blended map's range sizes the colour table).  Returns info:
+    base, n_midas, n_hole, blend_range, smoothed, range; None when no map is given."""
+    p = dict(FUSE_DEFAULTS)
+    unknown = set(params) - set(p)
+    if unknown:
+        raise TypeError(f"fuse_maps: unknown parameters {sorted(unknown)}")
+    p.update(params)
+    if d_stereo:
+        base = BASE_STEREO
+    elif d_midas:
+        base = BASE_MIDAS
+    elif d_flow:
+        base = BASE_FLOW
+    else:
+        return None
+    midas_fill = base == BASE_STEREO and bool(d_midas) and bool(p["use_midas_fill"])
+    flow_fill = base != BASE_FLOW and bool(d_flow) and bool(p["use_flow_fill"])
+    coef = gaussian_kernel(p["midas_blend_radius"]) if midas_fill else None
+    if midas_fill and (H <= coef.size // 2 or W <= coef.size // 2):
+        raise ValueError(f"fuse_maps: map {H}x{W} not larger than the blend radius {coef.size // 2}")
+    fw = float(p["flow_fill_weight"])
+    st = eng.fuse_blend_dev(
+        d_fused, H, W, base, d_stereo=d_stereo, d_conf=d_conf if base == BASE_STEREO else 0,
+        d_midas=d_midas if (base == BASE_MIDAS or midas_fill) else 0, d_flow=d_flow if (base == BASE_FLOW or flow_fill) else 0,
+        midas_fill=midas_fill, flow_fill=flow_fill, stereo_weight=p["stereo_weight"],
+        midas_fill_weight=p["midas_fill_weight"], conf_threshold=p["stereo_conf_threshold"],
+        hole_threshold=p["flow_hole_threshold"], flow_k1=1.0 - fw, flow_k2=fw, coef=coef, stream=stream)
+    mn, mx = st["min"], st["max"]
+    smoothed = bool(mx > 10.0)                                       # :1687
+    radius, sw, lut, scale = 0, None, None, 0.0
+    if smoothed and not abs(float(mx) - float(mn)) < FLT_EPSILON:
+        radius, sw, lut, scale = bilateral_tables(mn, mx, p["bilateral_d"], p["bilateral_sigma"],
+                                                  p["bilateral_sigma"])
+        if H <= radius or W <= radius:
+            raise ValueError(f"fuse_maps: map {H}x{W} not larger than the bilateral radius {radius}")
+    rng = eng.bilateral_f32_dev(d_fused, H, W, radius, sw, lut, scale, d_dst_u8=d_u8, d_dst_bgr=d_bgr,
+                                cmap=cmap if d_bgr else None, minmax=True, stream=stream)
+    return {"base": base, "midas_fill": midas_fill, "flow_fill": flow_fill, "n_midas": st["n_midas"],
+            "n_hole": st["n_hole"], "blend_range": (mn, mx), "smoothed": smoothed, "range": rng,
+            "params": p}
+
+
+def fuse_maps(stereo, conf, midas, flow, *, cmap=None, engine=None, **params):
+    """fuse_depth_maps' numeric body on host maps (None = absent): (fused_uint8, colormap,
+    info), colormap = cmap[fused_uint8] (None without a table); None when every map is None.
+    params: FUSE_DEFAULTS keys."""
+    (stereo, conf, midas, flow), shape = _check_maps(
+        "fuse_maps", [("stereo", stereo), ("conf", conf), ("midas", midas), ("flow", flow)])
+    if stereo is None and midas is None and flow is None:
+        return None
+    H, W = shape
+    eng = engine or get_engine()
+    n = H * W
+    up = lambda name, a: eng.upload(name, a) if a is not None else 0   # noqa: E731
+    d_fused = eng.scratch("fuse_f32", 4 * n)
+    d_u8 = eng.scratch("fuse_u8", n)
+    d_bgr = eng.scratch("fuse_bgr", 3 * n) if cmap is not None else 0
+    info = fuse_maps_dev(eng, H, W, up("fuse_stereo", stereo), up("fuse_conf", conf), up("fuse_midas", midas),
+                         up("fuse_flow", flow), d_fused, d_u8, d_bgr, cmap, **params)
+    u8 = eng.to_host(d_u8, (H, W), np.uint8)
+    bgr = eng.to_host(d_bgr, (H, W, 3), np.uint8) if d_bgr else None
+    return u8, bgr, info
 
 
 def normalize_to_stereo_range(depth_map, stereo_disparity):
