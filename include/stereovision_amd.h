@@ -37,6 +37,11 @@
  *                                    (fused_depth_map.py:1688, :2769, :1403-1411), optionally with
  *                                    the clip / uint8 / colormap / range block (:1696-1708)
  *   sv_fuse_blend_dev                the blend of fuse_depth_maps (fused_depth_map.py:1603-1684)
+ *   sv_farneback_flow_dev            cv2.calcOpticalFlowFarneback(prev, gray, None, 0.5, 3, 15, 3, 5,
+ *                                    1.2, 0) (fused_depth_map.py:1361-1370)
+ *   sv_flow_depth_dev                cv2.perspectiveTransform, the residual flow, 1 / (m + 0.5) and
+ *                                    the exponential average of OpticalFlowDepthEstimator
+ *                                    (fused_depth_map.py:1384-1400, :1492-1498)
  *   sv_multi_gpu_batch               the per-frame create_depth_map loop, frame-sharded over
  *                                    several devices from one process
  *   sv_rectify_pair                  the two remap calls of apply_stereo_rectification
@@ -100,7 +105,8 @@ enum sv_kernel {
     SV_K_H2D = 16,      /* host-buffer entry points: the frame pair's upload (per image) */
     SV_K_D2H = 17,      /* host-buffer entry points: the outputs' download */
     SV_K_FUSE = 18,     /* fuse_depth_maps: the blend, the Gaussian and the bilateral filter */
-    SV_NKERNELS = 19
+    SV_K_FLOW = 19,     /* Farneback optical flow and the flow depth (every launch of sv_flow.hip) */
+    SV_NKERNELS = 20
 };
 
 int sv_version(void);
@@ -553,6 +559,52 @@ typedef struct sv_fuse_stats {
 /* stats (host, nullable): the call then waits for the result. */
 int sv_fuse_blend_dev(sv_ctx* ctx, const sv_fuse_args* args, float* d_fused, sv_fuse_stats* stats,
                       void* stream);
+
+/* ---- Farneback optical flow and the flow depth estimator (fused_depth_map.py:1263-1501) ----
+ * cv2.calcOpticalFlowFarneback with flags = 0 and no initial flow, restated (DESIGN.md §9,
+ * "Optical flow"): bit-identical to the NumPy restatement of the tests; parity with a particular
+ * OpenCV build is unpinned.  Every exp and the inverse of the moment matrix are evaluated by the
+ * caller (flow.py: farneback_levels, gaussian_coef, polyexp_tables) and passed as host tables.
+ * Polynomial coefficients (R), the matrices (M) and a level's flow are dense float32 planes, H * W
+ * elements apart: R = (y, x, y^2, x^2, xy), M = (G11, G12, G22, h1, h2), flow = (dx, dy).
+ * All return SV_EINVAL before anything is enqueued for a null pointer or an argument outside the
+ * stated limits. */
+#define SV_FB_MAX_SCALES 16
+typedef struct sv_farneback_params {
+    int n_scales;              /* pyramid scales, 1..SV_FB_MAX_SCALES, finest first */
+    const int* scale_h;        /* host, n_scales entries each: the size of every scale (scale 0 = */
+    const int* scale_w;        /* H x W, no scale larger than the one before) and the ksize of its */
+    const int* scale_ksize;    /* Gaussian blur, odd in [3, 31] */
+    const float* scale_coef;   /* host, 32 floats per scale: the first ksize are the coefficients */
+    float flow_scale;          /* float32(1 / pyr_scale): factor on the upsampled flow */
+    int winsize;               /* odd in [3, 31] */
+    int iterations;            /* >= 1 */
+    int poly_n;                /* 5 or 7: 2 poly_n + 1 taps per axis */
+    const float* poly_g;       /* host, poly_n + 1 entries each: g[x], x g[x], x^2 g[x], x = 0.. */
+    const float* poly_xg;
+    const float* poly_xxg;
+    double ig[4];              /* ig11, ig03, ig33, ig55 of the inverse moment matrix */
+} sv_farneback_params;
+/* d_prev, d_next: gray uint8 H x W (H, W >= 16), rows `pitch` bytes apart; d_flow: float32
+ * H x W x 2.  Scratch comes from the context; nothing waits for the device. */
+int sv_farneback_flow_dev(sv_ctx* ctx, const uint8_t* d_prev, const uint8_t* d_next, int H, int W,
+                          int pitch, const sv_farneback_params* params, float* d_flow, void* stream);
+/* The stages alone.  polyexp: d_img float32 H x W -> d_R (5 planes).  update_matrices: d_flow
+ * = 2 planes -> d_M (5 planes).  blur_solve: d_M -> d_flow, 2 planes or (interleaved != 0)
+ * H x W x 2. */
+int sv_fb_polyexp_dev(sv_ctx* ctx, const float* d_img, int H, int W, int poly_n, const float* g,
+                      const float* xg, const float* xxg, const double ig[4], float* d_R, void* stream);
+int sv_fb_update_matrices_dev(sv_ctx* ctx, const float* d_R0, const float* d_R1, const float* d_flow,
+                              int H, int W, float* d_M, void* stream);
+int sv_fb_blur_solve_dev(sv_ctx* ctx, const float* d_M, int H, int W, int winsize, float* d_flow,
+                         int interleaved, void* stream);
+/* d_flow: H x W x 2.  e = perspectiveTransform((x, y), Hm) - (x, y) on float32 points (float64
+ * inside, w = 0 where |w| <= DBL_EPSILON); r = flow - e; m = float32(sqrt(rx^2 + ry^2)) with the
+ * squares and the root in float64; d_depth = 1 / (m + 0.5).  d_stable (nullable): stable = alpha
+ * * stable + one_minus_alpha * depth in float32.  minmax_out (host, nullable): min and max of
+ * d_depth; the call then waits for the result. */
+int sv_flow_depth_dev(sv_ctx* ctx, const float* d_flow, int H, int W, const double Hm[9], float* d_depth,
+                      float* d_stable, float alpha, float one_minus_alpha, float* minmax_out, void* stream);
 
 /* cv2.resize(x, (dW, dH), INTER_LINEAR) of a float32 HxW map (calibrate_midas_to_stereo,
  * fused_depth_map.py:1216-1217): OpenCV's float path, S0*b0 + S1*b1 without contraction.

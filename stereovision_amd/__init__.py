@@ -11,7 +11,8 @@ from .fusion import (bilateral_filter, bilateral_filter_dev, bilateral_tables, f
 
 __all__ = ["COSTS", "Engine", "EngineUnavailable", "SVError", "device_count", "get_engine",
            "load_library", "plan", "bilateral_filter", "bilateral_filter_dev", "bilateral_tables",
-           "fuse_maps", "fuse_maps_dev", "gaussian_blur", "gaussian_kernel", "fuse_depth_maps"]
+           "fuse_maps", "fuse_maps_dev", "gaussian_blur", "gaussian_kernel", "fuse_depth_maps",
+           "farneback_flow", "farneback_flow_dev", "OpticalFlowDepthEstimator"]
 
 
 def __getattr__(name):
@@ -19,4 +20,7 @@ def __getattr__(name):
     if name == "fuse_depth_maps":
         from .fused_depth_map import fuse_depth_maps
         return fuse_depth_maps
+    if name in ("farneback_flow", "farneback_flow_dev", "OpticalFlowDepthEstimator"):
+        from . import flow
+        return getattr(flow, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -1289,6 +1289,192 @@ int sv_fuse_blend_dev(sv_ctx* c, const sv_fuse_args* g, float* d_fused, sv_fuse_
     return 0;
 }
 
+// ---------------------------------------------------------------- Farneback optical flow
+static int fb_poly_tables(int poly_n, const float* g, const float* xg, const float* xxg, const double* ig,
+                          sv::FbPolyArgs* a) {
+    if (poly_n != 5 && poly_n != 7) return fail(SV_EINVAL, "poly_n must be 5 or 7");
+    if (!g || !xg || !xxg || !ig) return fail(SV_EINVAL, "null polynomial expansion tables");
+    a->n = poly_n;
+    for (int i = 0; i <= poly_n; ++i) {
+        a->g[i] = g[i];
+        a->xg[i] = xg[i];
+        a->xxg[i] = xxg[i];
+    }
+    a->ig11 = ig[0];
+    a->ig03 = ig[1];
+    a->ig33 = ig[2];
+    a->ig55 = ig[3];
+    return 0;
+}
+
+static int fb_winsize(int winsize) {
+    if (winsize < 3 || winsize > sv::kFbMaxWin || winsize % 2 == 0)
+        return fail(SV_EINVAL, "winsize must be odd in [3, 31]");
+    return 0;
+}
+
+int sv_fb_polyexp_dev(sv_ctx* c, const float* d_img, int H, int W, int poly_n, const float* g, const float* xg,
+                      const float* xxg, const double ig[4], float* d_R, void* stream) {
+    SV_ENTER(c);
+    if (!d_img || !d_R || H <= 0 || W <= 0) return fail(SV_EINVAL, "bad polynomial expansion arguments");
+    sv::FbPolyArgs a{};
+    int rc = fb_poly_tables(poly_n, g, xg, xxg, ig, &a);
+    if (rc) return rc;
+    a.src = d_img;
+    a.R = d_R;
+    a.plane = (size_t)H * W;
+    a.H = H;
+    a.W = W;
+    hipStream_t s = pick(c, stream);
+    SV_LAUNCH(c, SV_K_FLOW, s, sv::launch_fb_polyexp(a, s));
+    return 0;
+}
+
+int sv_fb_update_matrices_dev(sv_ctx* c, const float* d_R0, const float* d_R1, const float* d_flow, int H, int W,
+                              float* d_M, void* stream) {
+    SV_ENTER(c);
+    if (!d_R0 || !d_R1 || !d_flow || !d_M || H <= 0 || W <= 0)
+        return fail(SV_EINVAL, "bad update-matrices arguments");
+    sv::FbUpdateArgs a{d_R0, d_R1, d_flow, d_M, (size_t)H * W, H, W};
+    hipStream_t s = pick(c, stream);
+    SV_LAUNCH(c, SV_K_FLOW, s, sv::launch_fb_update_matrices(a, s));
+    return 0;
+}
+
+int sv_fb_blur_solve_dev(sv_ctx* c, const float* d_M, int H, int W, int winsize, float* d_flow, int interleaved,
+                         void* stream) {
+    SV_ENTER(c);
+    if (!d_M || !d_flow || H <= 0 || W <= 0) return fail(SV_EINVAL, "bad blur-solve arguments");
+    int rc = fb_winsize(winsize);
+    if (rc) return rc;
+    sv::FbSolveArgs a{d_M, (size_t)H * W, d_flow, interleaved ? 1 : 0, H, W, winsize / 2,
+                      1.0 / ((double)winsize * winsize)};
+    hipStream_t s = pick(c, stream);
+    SV_LAUNCH(c, SV_K_FLOW, s, sv::launch_fb_blur_solve(a, s));
+    return 0;
+}
+
+int sv_farneback_flow_dev(sv_ctx* c, const uint8_t* d_prev, const uint8_t* d_next, int H, int W, int pitch,
+                          const sv_farneback_params* p, float* d_flow, void* stream) {
+    SV_ENTER(c);
+    if (!d_prev || !d_next || !d_flow || !p) return fail(SV_EINVAL, "null optical-flow arguments");
+    if (H < 16 || W < 16) return fail(SV_EINVAL, "optical flow needs H, W >= 16");
+    if (pitch < W) return fail(SV_EINVAL, "pitch smaller than a row");
+    if (p->n_scales < 1 || p->n_scales > SV_FB_MAX_SCALES) return fail(SV_EINVAL, "1..16 pyramid scales");
+    if (!p->scale_h || !p->scale_w || !p->scale_ksize || !p->scale_coef)
+        return fail(SV_EINVAL, "null pyramid tables");
+    if (p->iterations < 1) return fail(SV_EINVAL, "iterations must be >= 1");
+    int rc = fb_winsize(p->winsize);
+    if (rc) return rc;
+    sv::FbPolyArgs poly{};
+    rc = fb_poly_tables(p->poly_n, p->poly_g, p->poly_xg, p->poly_xxg, p->ig, &poly);
+    if (rc) return rc;
+    if (p->scale_h[0] != H || p->scale_w[0] != W) return fail(SV_EINVAL, "pyramid scale 0 must be H x W");
+    sv::GaussArgs blur[SV_FB_MAX_SCALES];
+    for (int k = 0; k < p->n_scales; ++k) {
+        const int h = p->scale_h[k], w = p->scale_w[k];
+        if (h < 1 || w < 1 || (k > 0 && (h > p->scale_h[k - 1] || w > p->scale_w[k - 1])))
+            return fail(SV_EINVAL, "pyramid scales must be positive and not grow");
+        blur[k] = sv::GaussArgs{};
+        rc = gauss_coef(p->scale_coef + 32 * k, p->scale_ksize[k], H, W, blur[k].c);
+        if (rc) return rc;
+        blur[k].H = H;
+        blur[k].W = W;
+        blur[k].r = p->scale_ksize[k] / 2;
+    }
+    hipStream_t s = pick(c, stream);
+    SV_SCRATCH(c, s);
+    // floats: two converted frames, the blurred frame, the level image, R0, R1, M, two flows
+    const size_t N = (size_t)H * W;
+    SV_HIP(c->flow.ensure(23 * N * sizeof(float)));
+    float* base = c->flow.as<float>();
+    float* fimg[2] = {base, base + N};
+    float* blurred = base + 2 * N;
+    float* level = base + 3 * N;
+    float* R[2] = {base + 4 * N, base + 9 * N};
+    float* M = base + 14 * N;
+    float* fl[2] = {base + 19 * N, base + 21 * N};
+    const uint8_t* frames[2] = {d_prev, d_next};
+    for (int i = 0; i < 2; ++i) SV_LAUNCH(c, SV_K_FLOW, s, sv::launch_fb_u8_f32(frames[i], H, W, pitch, fimg[i], s));
+    int cur = 0;
+    for (int k = p->n_scales - 1; k >= 0; --k, cur ^= 1) {
+        const int h = p->scale_h[k], w = p->scale_w[k];
+        const size_t n = (size_t)h * w;
+        float* flow = fl[cur];
+        if (k == p->n_scales - 1) {
+            SV_HIP(hipMemsetAsync(flow, 0, 2 * n * sizeof(float), s));
+        } else {
+            const int ph = p->scale_h[k + 1], pw = p->scale_w[k + 1];
+            const float* prev = fl[cur ^ 1];
+            for (int comp = 0; comp < 2; ++comp)
+                SV_LAUNCH(c, SV_K_FLOW, s,
+                          sv::launch_resize_linear(prev + comp * (size_t)ph * pw, ph, pw, 1, pw * 4, 0, flow + comp * n,
+                                                   h, w, w * 4, 0, 1, true, s));
+            SV_LAUNCH(c, SV_K_FLOW, s, sv::launch_fb_scale(flow, 2 * n, p->flow_scale, s));
+        }
+        for (int i = 0; i < 2; ++i) {
+            sv::GaussArgs g = blur[k];
+            g.src = fimg[i];
+            g.dst = blurred;
+            SV_LAUNCH(c, SV_K_FLOW, s, sv::launch_gauss_f32(g, s));
+            const float* img = blurred;
+            if (h != H || w != W) {
+                SV_LAUNCH(c, SV_K_FLOW, s,
+                          sv::launch_resize_linear(blurred, H, W, 1, W * 4, 0, level, h, w, w * 4, 0, 1, true, s));
+                img = level;
+            }
+            sv::FbPolyArgs a = poly;
+            a.src = img;
+            a.R = R[i];
+            a.plane = n;
+            a.H = h;
+            a.W = w;
+            SV_LAUNCH(c, SV_K_FLOW, s, sv::launch_fb_polyexp(a, s));
+        }
+        sv::FbUpdateArgs u{R[0], R[1], flow, M, n, h, w};
+        SV_LAUNCH(c, SV_K_FLOW, s, sv::launch_fb_update_matrices(u, s));
+        for (int it = 0; it < p->iterations; ++it) {
+            const bool last = k == 0 && it == p->iterations - 1;
+            sv::FbSolveArgs b{M, n, last ? d_flow : flow, last ? 1 : 0, h, w, p->winsize / 2,
+                              1.0 / ((double)p->winsize * p->winsize)};
+            SV_LAUNCH(c, SV_K_FLOW, s, sv::launch_fb_blur_solve(b, s));
+            if (it < p->iterations - 1) SV_LAUNCH(c, SV_K_FLOW, s, sv::launch_fb_update_matrices(u, s));
+        }
+    }
+    return 0;
+}
+
+int sv_flow_depth_dev(sv_ctx* c, const float* d_flow, int H, int W, const double Hm[9], float* d_depth,
+                      float* d_stable, float alpha, float one_minus_alpha, float* minmax_out, void* stream) {
+    SV_ENTER(c);
+    if (!d_flow || !d_depth || !Hm || H <= 0 || W <= 0) return fail(SV_EINVAL, "bad flow-depth arguments");
+    if (d_stable == d_depth) return fail(SV_EINVAL, "flow depth: stable map aliases the depth map");
+    hipStream_t s = pick(c, stream);
+    SV_SCRATCH(c, s);
+    SV_HIP(c->fuse.ensure(kFuseBytes));
+    sv::FlowDepthArgs a{};
+    a.flow = d_flow;
+    a.depth = d_depth;
+    a.stable = d_stable;
+    a.stats = c->fuse.as<uint32_t>();
+    a.H = H;
+    a.W = W;
+    for (int i = 0; i < 9; ++i) a.m[i] = Hm[i];
+    a.alpha = alpha;
+    a.beta = one_minus_alpha;
+    SV_HIP(hipMemsetAsync(a.stats, 0, sv::kFuseStatsBytes, s));
+    SV_LAUNCH(c, SV_K_FLOW, s, sv::launch_flow_depth(a, s));
+    if (minmax_out) {
+        uint32_t slots[sv::kFuseSlots * sv::kFuseSlotStride], w[4];
+        SV_HIP(hipMemcpyAsync(slots, a.stats, sizeof(slots), hipMemcpyDeviceToHost, s));
+        SV_HIP(hipStreamSynchronize(s));
+        sv::fuse_stats_fold(slots, w);
+        minmax_out[0] = sv::fuse_stat_min(w);
+        minmax_out[1] = sv::fuse_stat_max(w);
+    }
+    return 0;
+}
+
 // ---------------------------------------------------------------- SGBM-3WAY mode
 int sv_sgbm_dev(sv_ctx* c, const uint8_t* d_left, const uint8_t* d_right, int H, int W, int pitch, int min_disp,
                 int num_disp, int block_size, int P1, int P2, int disp12_max_diff, int pre_filter_cap,

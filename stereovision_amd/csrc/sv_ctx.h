@@ -117,6 +117,7 @@ struct sv_ctx {
     DevBuf img[2], gray[2], d16, fa, fb, fc, u8, harris, hog[2], fin, lut, rmap1, rmap2, rdst[2], stats, sel,
         sg_hsum, sg_c, sg_l, sg_lt, sg_band, sg_rec, cc_parent, cc_size, hist_copies, cmap, bgr;
     DevBuf fuse;   // sv_fuse.hip: the accumulator copies (kFuseStatsBytes), then the bilateral colour table
+    DevBuf flow;   // sv_flow.hip: the pyramid images, R0, R1, M and two levels' flow of sv_farneback_flow_dev
     uint8_t cmap_host[768] = {};   // BGR table currently in `cmap`
     bool cmap_valid = false;
     // host-buffer frame path: int16 medians come back over PCIe and are expanded on the

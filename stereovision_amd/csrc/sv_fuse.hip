@@ -18,6 +18,7 @@
 // (w + 4 j, l), j = 0..3.  Four independent pixels per lane hide the serial tap sums, and a
 // lane's taps of one (dy, dx) are 64 consecutive LDS words per wave (no bank conflicts on
 // the tile; the colour-table lookups are data-dependent gathers and take what they get).
+#include "sv_fold.h"
 #include "sv_stencil.h"
 
 namespace sv {
@@ -26,42 +27,6 @@ namespace {
 constexpr int kTH = 16, kTW = 64, kPix = 4;
 constexpr int kGaussR = 15;                    // ksize <= 31
 constexpr int kBilPitch = kTW + 2 * kBilateralMaxR + 1;
-
-// order-preserving integer image of a finite float: a < b  <=>  fkey(a) < fkey(b)
-__device__ __forceinline__ uint32_t fkey(float v) {
-    const uint32_t u = __float_as_uint(v);
-    return u ^ ((u >> 31) ? 0xFFFFFFFFu : 0x80000000u);
-}
-
-// Accumulators of one launch, zero on entry: [0] max of ~fkey (the minimum), [1] max of fkey,
-// [2], [3] counts.  Per block: butterfly inside each wave, four partials through LDS, one
-// vector atomic per word into slot (block % kFuseSlots): thousands of same-address atomics
-// serialise at L2, so the blocks spread over kFuseSlots copies 128 B apart and the host folds
-// them (fuse_stats_fold).
-__device__ __forceinline__ void fold_stats(uint32_t kmin_inv, uint32_t kmax, uint32_t n0, uint32_t n1,
-                                           uint32_t (*red)[4], uint32_t* stats) {
-    for (int off = 32; off > 0; off >>= 1) {
-        kmin_inv = max(kmin_inv, (uint32_t)__shfl_xor((int)kmin_inv, off));
-        kmax = max(kmax, (uint32_t)__shfl_xor((int)kmax, off));
-        n0 += (uint32_t)__shfl_xor((int)n0, off);
-        n1 += (uint32_t)__shfl_xor((int)n1, off);
-    }
-    const int wave = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) {
-        red[wave][0] = kmin_inv;
-        red[wave][1] = kmax;
-        red[wave][2] = n0;
-        red[wave][3] = n1;
-    }
-    __syncthreads();
-    if (threadIdx.x < 4) {
-        const int k = threadIdx.x;
-        stats += ((blockIdx.y * gridDim.x + blockIdx.x) % kFuseSlots) * kFuseSlotStride;
-        const uint32_t a = red[0][k], b = red[1][k], c = red[2][k], d = red[3][k];
-        if (k < 2) atomicMax(&stats[k], max(max(a, b), max(c, d)));
-        else if (a + b + c + d) atomicAdd(&stats[k], a + b + c + d);
-    }
-}
 
 struct GaussTile {
     float in[kTH + 2 * kGaussR][kTW + 2 * kGaussR + 1];

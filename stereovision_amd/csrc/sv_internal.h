@@ -270,6 +270,50 @@ inline float fuse_stat_decode(uint32_t k) {
 inline float fuse_stat_min(const uint32_t* w) { return fuse_stat_decode(~w[0]); }
 inline float fuse_stat_max(const uint32_t* w) { return fuse_stat_decode(w[1]); }
 
+// Farneback optical flow and the flow depth estimator (sv_flow.hip; fused_depth_map.py:1263-1501,
+// DESIGN.md §9).  R, M and the per-level flow are planes, `plane` elements apart (>= H * W).
+constexpr int kFbMaxPolyN = 7;
+constexpr int kFbMaxWin = 31;
+struct FbPolyArgs {
+    const float* src;         // H x W, dense
+    float* R;                 // 5 planes
+    size_t plane;
+    int H, W, n;              // n = poly_n: 2 n + 1 taps per axis
+    float g[kFbMaxPolyN + 1], xg[kFbMaxPolyN + 1], xxg[kFbMaxPolyN + 1];
+    double ig11, ig03, ig33, ig55;
+};
+struct FbUpdateArgs {
+    const float* R0;          // 5 planes each
+    const float* R1;
+    const float* flow;        // 2 planes: dx, dy
+    float* M;                 // 5 planes
+    size_t plane;
+    int H, W;
+};
+struct FbSolveArgs {
+    const float* M;           // 5 planes
+    size_t plane;
+    float* flow;              // 2 planes, or H x W x 2 interleaved
+    int interleaved;
+    int H, W, m;              // m = winsize / 2
+    double scale;             // 1 / winsize^2
+};
+struct FlowDepthArgs {
+    const float* flow;        // H x W x 2
+    float* depth;
+    float* stable;            // nullable: stable = alpha * stable + beta * depth
+    uint32_t* stats;          // kFuseStatsBytes of accumulators of depth's range, zero on entry
+    int H, W;
+    double m[9];
+    float alpha, beta;
+};
+int launch_fb_u8_f32(const uint8_t* src, int H, int W, int pitch, float* dst, hipStream_t s);
+int launch_fb_scale(float* x, size_t n, float k, hipStream_t s);
+int launch_fb_polyexp(const FbPolyArgs& a, hipStream_t s);
+int launch_fb_update_matrices(const FbUpdateArgs& a, hipStream_t s);
+int launch_fb_blur_solve(const FbSolveArgs& a, hipStream_t s);
+int launch_flow_depth(const FlowDepthArgs& a, hipStream_t s);
+
 // SGBM-3WAY mode (sv_sgbm.hip).
 struct SgbmArgs {
     const uint8_t* L;

@@ -25,7 +25,8 @@ COSTS = {"sad": 0, "ssd": 1, "hog": 2, "sgbm": 3}
 POST_NONE, POST_DEPTH, POST_SCALED = 0, 1, 2
 KERNELS = {"gray": 0, "harris": 1, "hog": 2, "match": 3, "median": 4, "post": 5, "remap": 6,
            "undistort": 7, "resize": 8, "stats": 9, "select": 10, "affine": 11, "sgbm": 12,
-           "speckle": 13, "gather": 14, "scatter": 15, "h2d": 16, "d2h": 17, "fuse": 18}
+           "speckle": 13, "gather": 14, "scatter": 15, "h2d": 16, "d2h": 17, "fuse": 18,
+           "flow": 19}
 
 # Every symbol include/stereovision_amd.h declares (checked by tests/test_capi.py).
 EXPORTED = [
@@ -47,7 +48,8 @@ EXPORTED = [
     "sv_profile_region_end", "sv_comm_scatterv", "sv_band_rows_in", "sv_release_scratch",
     "sv_frame_stats_batch_dev", "sv_select_count_batch", "sv_select_ranks_batch", "sv_event_record",
     "sv_stream_wait_event", "sv_post_m16_dev", "sv_gauss_blur_f32_dev", "sv_bilateral_f32_dev",
-    "sv_fuse_blend_dev",
+    "sv_fuse_blend_dev", "sv_farneback_flow_dev", "sv_fb_polyexp_dev", "sv_fb_update_matrices_dev",
+    "sv_fb_blur_solve_dev", "sv_flow_depth_dev",
 ]
 BAND_MARGIN = 8   # SV_BAND_MARGIN: spare rows around a band-only input buffer
 COMM_ID_BYTES = 128
@@ -143,6 +145,14 @@ class FuseStats(ctypes.Structure):
     """sv_fuse_stats."""
     _fields_ = [("min", _c_float), ("max", _c_float), ("n_midas", ctypes.c_int64),
                 ("n_hole", ctypes.c_int64)]
+
+
+class FarnebackParams(ctypes.Structure):
+    """sv_farneback_params: the host tables of one sv_farneback_flow_dev call."""
+    _fields_ = [("n_scales", _c_int), ("scale_h", _vp), ("scale_w", _vp), ("scale_ksize", _vp),
+                ("scale_coef", _vp), ("flow_scale", _c_float), ("winsize", _c_int), ("iterations", _c_int),
+                ("poly_n", _c_int), ("poly_g", _vp), ("poly_xg", _vp), ("poly_xxg", _vp),
+                ("ig", ctypes.c_double * 4)]
 
 
 def map_out(mode: int = POST_NONE, disparity: int = 0, out_a: int = 0, out_u8: int = 0, out_b: int = 0,
@@ -250,6 +260,13 @@ def _declare(lib):
         "sv_bilateral_f32_dev": ([_vp, _vp, _c_int, _c_int, _c_int, _NullableF32, _NullableF32, _c_float,
                                   _vp, _vp, _vp, _NullableU8, _NullableF32, _vp], _c_int),
         "sv_fuse_blend_dev": ([_vp, ctypes.POINTER(FuseArgs), _vp, ctypes.POINTER(FuseStats), _vp], _c_int),
+        "sv_farneback_flow_dev": ([_vp, _vp, _vp, _c_int, _c_int, _c_int, ctypes.POINTER(FarnebackParams), _vp,
+                                   _vp], _c_int),
+        "sv_fb_polyexp_dev": ([_vp, _vp, _c_int, _c_int, _c_int, _f32p, _f32p, _f32p, _f64p, _vp, _vp], _c_int),
+        "sv_fb_update_matrices_dev": ([_vp, _vp, _vp, _vp, _c_int, _c_int, _vp, _vp], _c_int),
+        "sv_fb_blur_solve_dev": ([_vp, _vp, _c_int, _c_int, _c_int, _vp, _c_int, _vp], _c_int),
+        "sv_flow_depth_dev": ([_vp, _vp, _c_int, _c_int, _f64p, _vp, _vp, _c_float, _c_float, _NullableF32,
+                               _vp], _c_int),
         "sv_sgbm": ([_vp, _u8p, _u8p] + [_c_int] * 14 + [_i16p], _c_int),
         "sv_sgbm_dev": ([_vp, _vp, _vp] + [_c_int] * 13 + [_vp, _c_int, _vp], _c_int),
         "sv_filter_speckles": ([_vp, _i16p] + [_c_int] * 5, _c_int),
@@ -1112,6 +1129,70 @@ class Engine:
             return None
         return {"min": np.float32(st.min), "max": np.float32(st.max), "n_midas": int(st.n_midas),
                 "n_hole": int(st.n_hole)}
+
+    # -- Farneback optical flow and the flow depth (flow.py builds the tables) --------------------
+    def farneback_flow_dev(self, d_prev: int, d_next: int, H: int, W: int, pitch: int, scales, flow_scale,
+                           winsize: int, iterations: int, poly_n: int, poly_tables, d_flow: int,
+                           stream: int = 0):
+        """sv_farneback_flow_dev.  scales: [(h, w, ksize, coef float32[ksize])], finest first;
+        poly_tables: (g, xg, xxg, (ig11, ig03, ig33, ig55)).  d_flow: float32 H x W x 2."""
+        n = len(scales)
+        hs = np.array([s[0] for s in scales], np.int32)
+        ws = np.array([s[1] for s in scales], np.int32)
+        ks = np.array([s[2] for s in scales], np.int32)
+        coef = np.zeros((max(n, 1), 32), np.float32)
+        for i, s in enumerate(scales):
+            c = np.asarray(s[3], np.float32).ravel()
+            if c.size != s[2] or c.size > 32:
+                raise ValueError(f"scale {i}: {s[2]} Gaussian coefficients expected, got {c.size}")
+            coef[i, :c.size] = c
+        g, xg, xxg, ig = poly_tables
+        g, xg, xxg = (np.ascontiguousarray(t, np.float32) for t in (g, xg, xxg))
+        if min(g.size, xg.size, xxg.size) < int(poly_n) + 1:
+            raise ValueError("polynomial expansion tables shorter than poly_n + 1")
+        p = FarnebackParams()
+        p.n_scales = n
+        p.scale_h, p.scale_w, p.scale_ksize, p.scale_coef = hs.ctypes.data, ws.ctypes.data, ks.ctypes.data, coef.ctypes.data
+        p.flow_scale = np.float32(flow_scale)
+        p.winsize, p.iterations, p.poly_n = int(winsize), int(iterations), int(poly_n)
+        p.poly_g, p.poly_xg, p.poly_xxg = g.ctypes.data, xg.ctypes.data, xxg.ctypes.data
+        p.ig = (ctypes.c_double * 4)(*[float(v) for v in ig])
+        _check("sv_farneback_flow_dev", self.lib.sv_farneback_flow_dev(
+            self._h, d_prev, d_next, int(H), int(W), int(pitch), ctypes.byref(p), d_flow, stream or None))
+
+    def fb_polyexp_dev(self, d_img: int, H: int, W: int, poly_n: int, poly_tables, d_R: int, stream: int = 0):
+        """FarnebackPolyExp of a float32 device image into five planes (y, x, y^2, x^2, xy)."""
+        g, xg, xxg, ig = poly_tables
+        g, xg, xxg = (np.ascontiguousarray(t, np.float32) for t in (g, xg, xxg))
+        if min(g.size, xg.size, xxg.size) < int(poly_n) + 1:
+            raise ValueError("polynomial expansion tables shorter than poly_n + 1")
+        _check("sv_fb_polyexp_dev", self.lib.sv_fb_polyexp_dev(
+            self._h, d_img, int(H), int(W), int(poly_n), g, xg, xxg, np.array(ig, np.float64), d_R,
+            stream or None))
+
+    def fb_update_matrices_dev(self, d_R0: int, d_R1: int, d_flow: int, H: int, W: int, d_M: int,
+                               stream: int = 0):
+        """FarnebackUpdateMatrices: d_flow = 2 planes (dx, dy) -> d_M = 5 planes."""
+        _check("sv_fb_update_matrices_dev", self.lib.sv_fb_update_matrices_dev(
+            self._h, d_R0, d_R1, d_flow, int(H), int(W), d_M, stream or None))
+
+    def fb_blur_solve_dev(self, d_M: int, H: int, W: int, winsize: int, d_flow: int, interleaved: bool = False,
+                          stream: int = 0):
+        """FarnebackUpdateFlow_Blur's box sums and solve: d_M -> d_flow (planes, or H x W x 2)."""
+        _check("sv_fb_blur_solve_dev", self.lib.sv_fb_blur_solve_dev(
+            self._h, d_M, int(H), int(W), int(winsize), d_flow, int(bool(interleaved)), stream or None))
+
+    def flow_depth_dev(self, d_flow: int, H: int, W: int, Hm, d_depth: int, d_stable: int = 0, alpha=0.0,
+                       minmax: bool = True, stream: int = 0):
+        """Residual-flow depth 1 / (|flow - expected(Hm)| + 0.5) of an H x W x 2 device flow, and
+        (d_stable) stable = float32(alpha) stable + float32(1 - alpha) depth; minmax: waits and
+        returns (min, max) of the depth map."""
+        Hm = np.ascontiguousarray(Hm, np.float64).reshape(9)
+        mm = np.zeros(2, np.float32) if minmax else None
+        _check("sv_flow_depth_dev", self.lib.sv_flow_depth_dev(
+            self._h, d_flow, int(H), int(W), Hm, d_depth, d_stable or None, np.float32(alpha),
+            np.float32(1.0 - float(alpha)), mm, stream or None))
+        return (mm[0], mm[1]) if minmax else None
 
     def rectify_pair(self, dmaps, left, right):
         """Both remaps of apply_stereo_rectification with device-resident maps

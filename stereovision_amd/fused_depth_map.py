@@ -15,6 +15,10 @@ settings (``FUSION_*``, ``fusion_params``, read at call time) and return value a
 blend, Gaussian fill weight, bilateral filter, quantisation and colormap run on the GPU
 (``fusion.fuse_maps``).
 
+``OpticalFlowDepthEstimator`` (fused_depth_map.py:1263-1501), the producer of
+``flow_depth_normalized``, is ``flow.OpticalFlowDepthEstimator``: Farneback flow, residual depth
+and the bilateral filter on the GPU, the RANSAC homography on the host.
+
 The reference calls the stereo function from a ThreadPoolExecutor worker and waits at most
 0.5 s (fused_depth_map.py:2591-2598, :2671); :func:`warmup` builds the engine and runs
 the scaled path once at the processing size, so the first real frame does not pay HIP
@@ -30,11 +34,13 @@ import traceback
 import numpy as np
 
 from . import colormap
+from . import flow as _flow
 from . import fusion as _fusion
 from . import rectify as _rectify
 from .fusion import (calibrate_midas_to_stereo, detect_camera_occlusion,  # noqa: F401
                      normalize_to_stereo_range)
 from .engine import get_engine, start_warmup
+from .flow import OpticalFlowDepthEstimator  # noqa: F401
 from .preamble import ensure_same_size, to_engine_image
 
 STEREO_CALIBRATION_FILE = "output/stereo_calibration_data.pkl"   # fused_depth_map.py:61
@@ -176,7 +182,12 @@ def warmup(height: int = 356, width: int = 633, processing_scale: float = None) 
     the camera delivers them."""
     nd, ws = scaled_stereo_params(processing_scale)
     z = np.zeros((height, width, 3), np.uint8)
-    get_engine().stereo_scaled_color(z, z, MIN_DISP_BASE, nd, ws, colormap.table("jet"), cost=COST)
+    eng = get_engine()
+    eng.stereo_scaled_color(z, z, MIN_DISP_BASE, nd, ws, colormap.table("jet"), cost=COST)
+    # one optical-flow step, so the estimator's first pair does not load the flow kernels' code
+    # objects and allocate their scratch inside the caller's budget
+    if height >= 16 and width >= 16:
+        _flow.farneback_flow(z[..., 0], z[..., 0], *_flow.OpticalFlowDepthEstimator.FLOW_ARGS, engine=eng)
 
 
 warmup_done = None
