@@ -136,8 +136,10 @@ int sv_plan(int num_disp, int win, int cost, int* dpl, int* lpg, int* lds_bytes)
 int sv_gray(sv_ctx* ctx, const uint8_t* bgr, int H, int W, int stride, uint8_t* gray);
 
 /* left/right: HxW (channels = 1) or HxWx3 BGR (channels = 3).  disp16: HxW int16 = d*16,
- * invalid = (min_disp-1)*16.  harris (nullable): HxW f32 Harris response of the left
- * gray image. */
+ * invalid = (min_disp-1)*16.  Every entry point that computes a disparity map, for every
+ * cost, requires min_disp >= -2047 and min_disp + num_disp - 1 <= 2047, so that the invalid
+ * value and the largest disparity both fit the int16 x16 map (SV_EINVAL otherwise).
+ * harris (nullable): HxW f32 Harris response of the left gray image. */
 int sv_disparity(sv_ctx* ctx, const uint8_t* left, const uint8_t* right, int H, int W,
                  int channels, int stride, int min_disp, int num_disp, int win, int cost,
                  int16_t* disp16, float* harris);
@@ -442,7 +444,8 @@ int sv_resize_linear_dev(sv_ctx* ctx, const uint8_t* d_src, int sH, int sW, int 
  * preFilterCap, uniquenessRatio, speckleWindowSize, speckleRange, MODE_SGBM_3WAY)
  * .compute(left, right) (depth_map.py:894-909): int16 x16 map, invalid = (minD-1)*16.
  * Semantics in oracle/sv_sgbm_oracle.py (one stripe; int32 aggregation).  Limits:
- * num_disp <= 512, block_size odd <= 15, P2 < 349525, P1 < P2 (P2 = max(P2, P1+1)).
+ * num_disp <= 512, block_size odd <= 15, P2 < 349525, P1 < P2 (P2 = max(P2, P1+1)),
+ * W <= 16384, min_disp >= -2047 and min_disp + num_disp - 1 <= 2047 (the int16 x16 map).
  * disp12MaxDiff < 0 disables the left-right check; speckleWindowSize <= 0 the filter. */
 int sv_sgbm(sv_ctx* ctx, const uint8_t* left, const uint8_t* right, int H, int W, int channels,
             int stride, int min_disp, int num_disp, int block_size, int P1, int P2,

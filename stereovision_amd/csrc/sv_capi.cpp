@@ -34,7 +34,11 @@ int check_match(int H, int W, int min_disp, int num_disp, int win, int cost, sv:
     if (H <= 0 || W <= 0) return fail(SV_EINVAL, "non-positive image size");
     if (num_disp <= 0 || num_disp > 512) return fail(SV_EINVAL, "num_disp must be in [1, 512]");
     if (win < 1 || win > 15 || (win & 1) == 0) return fail(SV_EINVAL, "win must be odd in [1, 15]");
-    if (min_disp < -4096 || min_disp > 4096) return fail(SV_EINVAL, "min_disp out of range");
+    // the int16 x16 map of every cost holds (min_disp - 1) * 16 (invalid) up to
+    // (min_disp + num_disp - 1) * 16: beyond [-32768, 32752] both ends would wrap
+    if (min_disp < -2047 || min_disp + num_disp - 1 > 2047)
+        return fail(SV_EINVAL, "disparity range beyond the int16 x16 map: min_disp >= -2047 and "
+                               "min_disp + num_disp - 1 <= 2047 required");
     if (cost == SV_COST_SGBM) return 0;   // no lane plan: sv_sgbm.hip sizes itself
     int rc = sv::plan_match(num_disp, win, cost, plan);
     if (rc == -34) return fail(SV_ERANGE, "cost range too large for the argmin key");

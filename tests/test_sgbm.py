@@ -86,8 +86,19 @@ def test_gpu_sgbm_int32_paths_window15(engine):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("H,W", [(1, 40), (2, 33), (5, 17), (30, 20)])
-def test_gpu_sgbm_ragged(engine, H, W):
+@pytest.mark.parametrize("H,W,shifted", [pytest.param(H, W, s, id=f"{H}-{W}" + ("-shifted" if s else ""))
+                                         for s in (False, True)
+                                         for H, W in [(1, 40), (2, 33), (5, 17), (30, 20)]])
+def test_gpu_sgbm_ragged(engine, H, W, shifted):
+    """shifted=False: independent noise with the default filters, which leave 0 % of the band
+    valid at the three smallest shapes (speckleWindowSize = 100 exceeds the band); shifted=True:
+    R a shifted copy of L and no speckle filter, >= 25 % valid (tests/test_sgbm_bar.py, B7)."""
+    if shifted:
+        from sgbm_frames import ragged_shifted
+        L, R = ragged_shifted(H, W)
+        np.testing.assert_array_equal(engine.sgbm(L, R, 0, 16, 3, speckle_window_size=0),
+                                      SG.sgbm(L, R, 0, 16, 3, speckleWindowSize=0))
+        return
     rng = np.random.default_rng(H * W)
     L = rng.integers(0, 256, (H, W), dtype=np.uint8)
     R = rng.integers(0, 256, (H, W), dtype=np.uint8)
