@@ -42,6 +42,11 @@
  *   sv_flow_depth_dev                cv2.perspectiveTransform, the residual flow, 1 / (m + 0.5) and
  *                                    the exponential average of OpticalFlowDepthEstimator
  *                                    (fused_depth_map.py:1384-1400, :1492-1498)
+ *   sv_flow_grid_dev                 the flow at the ego-motion grid of _estimate_ego_motion
+ *                                    (fused_depth_map.py:1447-1455)
+ *   sv_affine_f32_dev modes 3-5      the frame loop's normalisations of the flow depth and of the
+ *                                    MiDaS map without stereo (fused_depth_map.py:2749-2759,
+ *                                    :2793-2811)
  *   sv_multi_gpu_batch               the per-frame create_depth_map loop, frame-sharded over
  *                                    several devices from one process
  *   sv_rectify_pair                  the two remap calls of apply_stereo_rectification
@@ -503,7 +508,10 @@ int sv_select_ranks_batch(sv_ctx* ctx, const float* d_x, int64_t n, int64_t x_st
                           int mask_mode, const float* d_mask, int64_t mask_stride, float thr,
                           const int64_t* ranks, int nranks, float* values);
 /* Elementwise epilogues: mode 0: out = fc + ((x - fa) / fb) * fd in float32, op by op;
- * mode 1: out = float32(float64(x) * ds + doff); mode 2: out = fc. */
+ * mode 1: out = float32(float64(x) * ds + doff); mode 2: out = fc.  The frame loop's
+ * normalisations (fused_depth_map.py:2749-2759, :2793-2811), float32 op by op, np.clip keeping a
+ * NaN: mode 3: out = 255 - (mode 0); mode 4: out = 255 - clip(x * 255, 0, 255); mode 5: out =
+ * clip(((x - fa) / fb) * 255, 0, 255). */
 int sv_affine_f32_dev(sv_ctx* ctx, const float* d_x, int64_t n, int mode, float fa, float fb,
                       float fc, float fd, double ds, double doff, float* d_out, void* stream);
 
@@ -608,6 +616,11 @@ int sv_fb_blur_solve_dev(sv_ctx* ctx, const float* d_M, int H, int W, int winsiz
  * d_depth; the call then waits for the result. */
 int sv_flow_depth_dev(sv_ctx* ctx, const float* d_flow, int H, int W, const double Hm[9], float* d_depth,
                       float* d_stable, float alpha, float one_minus_alpha, float* minmax_out, void* stream);
+/* The flow at the grid of _estimate_ego_motion (fused_depth_map.py:1447-1455): d_out[j * nx + i]
+ * = d_flow[step / 2 + j * step][step / 2 + i * step] (both components), ny = the number of grid
+ * rows below H, nx of grid columns below W; d_out holds ny * nx * 2 floats.  Both pointers
+ * 8-byte aligned.  A host then downloads the grid instead of the H x W x 2 flow. */
+int sv_flow_grid_dev(sv_ctx* ctx, const float* d_flow, int H, int W, int step, float* d_out, void* stream);
 
 /* cv2.resize(x, (dW, dH), INTER_LINEAR) of a float32 HxW map (calibrate_midas_to_stereo,
  * fused_depth_map.py:1216-1217): OpenCV's float path, S0*b0 + S1*b1 without contraction.
@@ -624,6 +637,12 @@ int sv_dev_alloc(sv_ctx* ctx, uint64_t bytes, void** out);
 int sv_dev_free(sv_ctx* ctx, void* p);
 int sv_copy_to_device(sv_ctx* ctx, void* dst, const void* src, uint64_t bytes, void* stream);
 int sv_copy_to_host(sv_ctx* ctx, void* dst, const void* src, uint64_t bytes, void* stream);
+/* Host <-> device traffic of this context since its creation (or the last reset): out[0], out[1]
+ * = bytes and calls of the host-to-device copies, out[2], out[3] = of the device-to-host copies.
+ * Every copy the library issues for the context counts, the scalar read-backs inside the `_dev`
+ * entry points (blend statistics, min/max, select counts) included.  reset != 0: zero them after
+ * reading.  Plain host counters: no device work. */
+int sv_copy_counters(sv_ctx* ctx, uint64_t out[4], int reset);
 
 /* Page-lock a host range and make it device-visible (hipHostRegister, portable).  Output
  * arrays of the host-buffer entry points (sv_depth_map, sv_depth_map_color,

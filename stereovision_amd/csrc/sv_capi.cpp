@@ -331,7 +331,7 @@ int attach_cmap(sv_ctx* c, sv::PostParams& pp, const uint8_t* table, uint8_t* d_
         uint32_t packed[256];
         for (int i = 0; i < 256; ++i)
             packed[i] = (uint32_t)table[3 * i] | ((uint32_t)table[3 * i + 1] << 8) | ((uint32_t)table[3 * i + 2] << 16);
-        SV_HIP(hipMemcpyAsync(c->cmap.p, packed, sizeof(packed), hipMemcpyHostToDevice, s));
+        SV_HIP(c->copy(c->cmap.p, packed, sizeof(packed), hipMemcpyHostToDevice, s));
         SV_HIP(hipStreamSynchronize(s));   // `packed` lives on this stack frame
         std::memcpy(c->cmap_host, table, 768);
         c->cmap_valid = true;
@@ -430,13 +430,13 @@ int stage_pair(sv_ctx* c, const uint8_t* left, const uint8_t* right, int H, int 
         }
     }
     if (channels == 1) {
-        SV_HIP(hipMemcpyAsync(c->gray[0].p, c->hin.p, n, hipMemcpyHostToDevice, c->stream));
-        SV_HIP(hipMemcpyAsync(c->gray[1].p, c->hin.as<uint8_t>() + n, n, hipMemcpyHostToDevice, c->stream));
+        SV_HIP(c->copy(c->gray[0].p, c->hin.p, n, hipMemcpyHostToDevice, c->stream));
+        SV_HIP(c->copy(c->gray[1].p, c->hin.as<uint8_t>() + n, n, hipMemcpyHostToDevice, c->stream));
     } else {
         SV_HIP(c->img[0].ensure(n));
         SV_HIP(c->img[1].ensure(n));
         for (int k = 0; k < 2; ++k) {
-            SV_HIP(hipMemcpyAsync(c->img[k].p, c->hin.as<uint8_t>() + k * n, n, hipMemcpyHostToDevice, c->stream));
+            SV_HIP(c->copy(c->img[k].p, c->hin.as<uint8_t>() + k * n, n, hipMemcpyHostToDevice, c->stream));
             SV_LAUNCH(c, SV_K_GRAY, c->stream,
                       sv::launch_gray(c->img[k].as<uint8_t>(), H, W, (int)row, c->gray[k].as<uint8_t>(), c->stream));
         }
@@ -453,7 +453,7 @@ int collect(sv_ctx* c, const Out* outs, int n) {
     size_t off = 0;
     for (int i = 0; i < n; ++i) {
         if (!outs[i].host) continue;
-        SV_HIP(hipMemcpyAsync(c->hout.as<uint8_t>() + off, outs[i].dev, outs[i].bytes, hipMemcpyDeviceToHost, c->stream));
+        SV_HIP(c->copy(c->hout.as<uint8_t>() + off, outs[i].dev, outs[i].bytes, hipMemcpyDeviceToHost, c->stream));
         off += (outs[i].bytes + 255) & ~(size_t)255;
     }
     SV_HIP(hipStreamSynchronize(c->stream));
@@ -675,10 +675,10 @@ int sv_copy_to_device(sv_ctx* c, void* dst, const void* src, uint64_t bytes, voi
     if (!dst || !src) return fail(SV_EINVAL, "null pointer");
     if (!bytes) return 0;
     if (stream) {   // enqueued: the caller keeps src alive (and pinned, for overlap)
-        SV_HIP(hipMemcpyAsync(dst, src, (size_t)bytes, hipMemcpyHostToDevice, static_cast<hipStream_t>(stream)));
+        SV_HIP(c->copy(dst, src, (size_t)bytes, hipMemcpyHostToDevice, static_cast<hipStream_t>(stream)));
         return 0;
     }
-    SV_HIP(hipMemcpyAsync(dst, src, (size_t)bytes, hipMemcpyHostToDevice, c->stream));
+    SV_HIP(c->copy(dst, src, (size_t)bytes, hipMemcpyHostToDevice, c->stream));
     SV_HIP(hipStreamSynchronize(c->stream));
     return 0;
 }
@@ -688,12 +688,22 @@ int sv_copy_to_host(sv_ctx* c, void* dst, const void* src, uint64_t bytes, void*
     if (!dst || !src) return fail(SV_EINVAL, "null pointer");
     if (!bytes) return 0;
     if (stream) {
-        SV_HIP(hipMemcpyAsync(dst, src, (size_t)bytes, hipMemcpyDeviceToHost, static_cast<hipStream_t>(stream)));
+        SV_HIP(c->copy(dst, src, (size_t)bytes, hipMemcpyDeviceToHost, static_cast<hipStream_t>(stream)));
         return 0;
     }
     SV_HIP(hipStreamSynchronize(c->stream));   // results of enqueued device work
-    SV_HIP(hipMemcpyAsync(dst, src, (size_t)bytes, hipMemcpyDeviceToHost, c->stream));
+    SV_HIP(c->copy(dst, src, (size_t)bytes, hipMemcpyDeviceToHost, c->stream));
     SV_HIP(hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+int sv_copy_counters(sv_ctx* c, uint64_t out[4], int reset) {
+    SV_ENTER(c);
+    if (!out) return fail(SV_EINVAL, "null pointer");
+    for (int i = 0; i < 4; ++i) {
+        out[i] = c->copy_ctr[i];
+        if (reset) c->copy_ctr[i] = 0;
+    }
     return 0;
 }
 

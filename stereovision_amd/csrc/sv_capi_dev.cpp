@@ -180,7 +180,7 @@ int sv_gray(sv_ctx* c, const uint8_t* bgr, int H, int W, int stride, uint8_t* gr
     for (int y = 0; y < H; ++y) std::memcpy(c->hin.as<uint8_t>() + y * row, bgr + (size_t)y * stride, row);
     SV_HIP(c->img[0].ensure(n));
     SV_HIP(c->gray[0].ensure((size_t)H * W));
-    SV_HIP(hipMemcpyAsync(c->img[0].p, c->hin.p, n, hipMemcpyHostToDevice, c->stream));
+    SV_HIP(c->copy(c->img[0].p, c->hin.p, n, hipMemcpyHostToDevice, c->stream));
     SV_LAUNCH(c, SV_K_GRAY, c->stream,
               sv::launch_gray(c->img[0].as<uint8_t>(), H, W, (int)row, c->gray[0].as<uint8_t>(), c->stream));
     Out o[] = {{gray, c->gray[0].p, (size_t)H * W}};
@@ -244,7 +244,7 @@ int sv_median5_f32(sv_ctx* c, const float* in, int H, int W, float* out) {
     SV_HIP(c->fin.ensure(n));
     SV_HIP(c->fa.ensure(n));
     std::memcpy(c->hin.p, in, n);
-    SV_HIP(hipMemcpyAsync(c->fin.p, c->hin.p, n, hipMemcpyHostToDevice, c->stream));
+    SV_HIP(c->copy(c->fin.p, c->hin.p, n, hipMemcpyHostToDevice, c->stream));
     SV_LAUNCH(c, SV_K_MEDIAN, c->stream, sv::launch_median_f32(c->fin.as<float>(), H, W, c->fa.as<float>(), c->stream));
     Out o[] = {{out, c->fa.p, n}};
     return collect(c, o, 1);
@@ -260,7 +260,7 @@ static int post_common(sv_ctx* c, const float* disparity, int n, const sv::PostP
     SV_HIP(c->fb.ensure(nb));
     SV_HIP(c->u8.ensure((size_t)n));
     std::memcpy(c->hin.p, disparity, nb);
-    SV_HIP(hipMemcpyAsync(c->fin.p, c->hin.p, nb, hipMemcpyHostToDevice, c->stream));
+    SV_HIP(c->copy(c->fin.p, c->hin.p, nb, hipMemcpyHostToDevice, c->stream));
     sv::PostParams pp = tmpl;
     pp.out_a = c->fa.as<float>();
     pp.out_u8 = c->u8.as<uint8_t>();
@@ -325,8 +325,8 @@ int stage_rows(sv_ctx* c, const uint8_t* src, int y0, int y1, size_t row, int st
     // gpurun_out/host3; round 4 the same rates either way, profiles/r04_misc/
     // host_stage_ab_r04h.txt); strided rows take the pinned copy.
     if ((size_t)stride == row) {
-        SV_HIP(hipMemcpyAsync(dev + (size_t)y0 * row, src + (size_t)y0 * row, (size_t)(y1 - y0) * row,
-                              hipMemcpyHostToDevice, c->stream));
+        SV_HIP(c->copy(dev + (size_t)y0 * row, src + (size_t)y0 * row, (size_t)(y1 - y0) * row,
+                       hipMemcpyHostToDevice, c->stream));
         return 0;
     }
     sv::HostPool& pool = sv::HostPool::get();
@@ -342,8 +342,8 @@ int stage_rows(sv_ctx* c, const uint8_t* src, int y0, int y1, size_t row, int st
             else
                 for (int y = a; y < b; ++y) std::memcpy(stage + (size_t)y * row, src + (size_t)y * stride, row);
         });
-        SV_HIP(hipMemcpyAsync(dev + (size_t)a0 * row, stage + (size_t)a0 * row, (size_t)(a1 - a0) * row,
-                              hipMemcpyHostToDevice, c->stream));
+        SV_HIP(c->copy(dev + (size_t)a0 * row, stage + (size_t)a0 * row, (size_t)(a1 - a0) * row,
+                       hipMemcpyHostToDevice, c->stream));
     }
     return 0;
 }
@@ -359,9 +359,9 @@ int host_lut(sv_ctx* c, const sv::PostParams& pp) {
     } catch (...) {
         return fail(SV_ENOMEM, "host table allocation failed");
     }
-    SV_HIP(hipMemcpyAsync(c->hl_a.data(), pp.lut_a, n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-    SV_HIP(hipMemcpyAsync(c->hl_b.data(), pp.lut_b, n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-    SV_HIP(hipMemcpyAsync(c->hl_u8.data(), pp.lut_u8, n, hipMemcpyDeviceToHost, c->stream));
+    SV_HIP(c->copy(c->hl_a.data(), pp.lut_a, n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    SV_HIP(c->copy(c->hl_b.data(), pp.lut_b, n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    SV_HIP(c->copy(c->hl_u8.data(), pp.lut_u8, n, hipMemcpyDeviceToHost, c->stream));
     SV_HIP(hipStreamSynchronize(c->stream));
     c->hl_key = c->lut_key;
     c->hl_valid = true;
@@ -603,15 +603,15 @@ int host_frame_path(sv_ctx* c, const uint8_t* left, const uint8_t* right, int H,
             if (p1 <= p0) continue;
             const size_t i0 = (size_t)p0 * W, m = (size_t)(p1 - p0) * W;
             if (reg) {
-                SV_HIP(hipMemcpyAsync(o.disp + i0, c->fb.as<float>() + i0, m * 4, hipMemcpyDeviceToHost, ds));
-                SV_HIP(hipMemcpyAsync(o.a + i0, c->fa.as<float>() + i0, m * 4, hipMemcpyDeviceToHost, ds));
-                if (o.u8) SV_HIP(hipMemcpyAsync(o.u8 + i0, c->u8.as<uint8_t>() + i0, m, hipMemcpyDeviceToHost, ds));
-                if (scaled) SV_HIP(hipMemcpyAsync(o.b + i0, c->fc.as<float>() + i0, m * 4, hipMemcpyDeviceToHost, ds));
+                SV_HIP(c->copy(o.disp + i0, c->fb.as<float>() + i0, m * 4, hipMemcpyDeviceToHost, ds));
+                SV_HIP(c->copy(o.a + i0, c->fa.as<float>() + i0, m * 4, hipMemcpyDeviceToHost, ds));
+                if (o.u8) SV_HIP(c->copy(o.u8 + i0, c->u8.as<uint8_t>() + i0, m, hipMemcpyDeviceToHost, ds));
+                if (scaled) SV_HIP(c->copy(o.b + i0, c->fc.as<float>() + i0, m * 4, hipMemcpyDeviceToHost, ds));
                 if (o.bgr)
-                    SV_HIP(hipMemcpyAsync(o.bgr + 3 * i0, c->bgr.as<uint8_t>() + 3 * i0, 3 * m, hipMemcpyDeviceToHost, ds));
+                    SV_HIP(c->copy(o.bgr + 3 * i0, c->bgr.as<uint8_t>() + 3 * i0, 3 * m, hipMemcpyDeviceToHost, ds));
             } else {
-                SV_HIP(hipMemcpyAsync(c->hout.as<int16_t>() + i0, c->m16.as<int16_t>() + i0, m * 2, hipMemcpyDeviceToHost,
-                                      ds));
+                SV_HIP(c->copy(c->hout.as<int16_t>() + i0, c->m16.as<int16_t>() + i0, m * 2, hipMemcpyDeviceToHost,
+                               ds));
                 if (!c->dev_done[q]) SV_HIP(hipEventCreateWithFlags(&c->dev_done[q], hipEventDisableTiming));
                 SV_HIP(hipEventRecord(c->dev_done[q], ds));
             }
@@ -741,7 +741,7 @@ int sv_harris(sv_ctx* c, const uint8_t* gray, int H, int W, int stride, float* o
     for (int y = 0; y < H; ++y) std::memcpy(c->hin.as<uint8_t>() + (size_t)y * W, gray + (size_t)y * stride, W);
     SV_HIP(c->gray[0].ensure(n));
     SV_HIP(c->harris.ensure(n * sizeof(float)));
-    SV_HIP(hipMemcpyAsync(c->gray[0].p, c->hin.p, n, hipMemcpyHostToDevice, c->stream));
+    SV_HIP(c->copy(c->gray[0].p, c->hin.p, n, hipMemcpyHostToDevice, c->stream));
     SV_LAUNCH(c, SV_K_HARRIS, c->stream,
               sv::launch_harris(c->gray[0].as<uint8_t>(), H, W, W, c->harris.as<float>(), c->stream));
     Out o[] = {{out, c->harris.p, n * sizeof(float)}};
@@ -758,7 +758,7 @@ int sv_hog_hist(sv_ctx* c, const uint8_t* gray, int H, int W, int stride, int wi
     for (int y = 0; y < H; ++y) std::memcpy(c->hin.as<uint8_t>() + (size_t)y * W, gray + (size_t)y * stride, W);
     SV_HIP(c->gray[0].ensure(n));
     SV_HIP(c->hog[0].ensure(n * 10 * sizeof(uint16_t)));
-    SV_HIP(hipMemcpyAsync(c->gray[0].p, c->hin.p, n, hipMemcpyHostToDevice, c->stream));
+    SV_HIP(c->copy(c->gray[0].p, c->hin.p, n, hipMemcpyHostToDevice, c->stream));
     SV_LAUNCH(c, SV_K_HOG, c->stream,
               sv::launch_hog_hist(c->gray[0].as<uint8_t>(), H, W, W, win, 0, H, c->hog[0].as<uint16_t>(), c->stream));
     Out o[] = {{out, c->hog[0].p, n * 10 * sizeof(uint16_t)}};
@@ -832,7 +832,7 @@ static int remap_host_common(sv_ctx* c, const uint8_t* const* srcs, int nimg, in
         } else {
             for (int y = 0; y < sH; ++y) std::memcpy(dst + y * row, srcs[k] + (size_t)y * stride, row);
         }
-        SV_HIP(hipMemcpyAsync(c->img[k].p, dst, n, hipMemcpyHostToDevice, c->stream));
+        SV_HIP(c->copy(c->img[k].p, dst, n, hipMemcpyHostToDevice, c->stream));
     }
     const size_t on = (size_t)H * W * channels;
     Out o[2];
@@ -855,8 +855,8 @@ int sv_remap(sv_ctx* c, const uint8_t* src, int sH, int sW, int channels, int st
     const size_t n = (size_t)H * W;
     SV_HIP(c->rmap1.ensure(n * 4));
     SV_HIP(c->rmap2.ensure(n * 2));
-    SV_HIP(hipMemcpyAsync(c->rmap1.p, map1, n * 4, hipMemcpyHostToDevice, c->stream));
-    if (map2) SV_HIP(hipMemcpyAsync(c->rmap2.p, map2, n * 2, hipMemcpyHostToDevice, c->stream));
+    SV_HIP(c->copy(c->rmap1.p, map1, n * 4, hipMemcpyHostToDevice, c->stream));
+    if (map2) SV_HIP(c->copy(c->rmap2.p, map2, n * 2, hipMemcpyHostToDevice, c->stream));
     const short2* m1[1] = {c->rmap1.as<short2>()};
     const uint16_t* m2[1] = {map2 ? c->rmap2.as<uint16_t>() : nullptr};
     const uint8_t* srcs[1] = {src};
@@ -922,7 +922,7 @@ int sv_resize_linear(sv_ctx* c, const uint8_t* src, int sH, int sW, int channels
     SV_HIP(c->img[0].ensure(n));
     const size_t on = (size_t)dH * dW * channels;
     SV_HIP(c->rdst[0].ensure(on));
-    SV_HIP(hipMemcpyAsync(c->img[0].p, c->hin.p, n, hipMemcpyHostToDevice, c->stream));
+    SV_HIP(c->copy(c->img[0].p, c->hin.p, n, hipMemcpyHostToDevice, c->stream));
     SV_LAUNCH(c, SV_K_RESIZE, c->stream,
               sv::launch_resize_linear(c->img[0].as<uint8_t>(), sH, sW, channels, (int)row, 0,
                                        c->rdst[0].as<uint8_t>(), dH, dW, dW * channels, 0, 1, false, c->stream));
@@ -987,7 +987,7 @@ int sv_frame_stats(sv_ctx* c, const uint8_t* img0, const uint8_t* img1, int H, i
         SV_HIP(c->img[k].ensure(n));
         uint8_t* dst = c->hin.as<uint8_t>() + k * n;
         for (int y = 0; y < H; ++y) std::memcpy(dst + y * row, src[k] + (size_t)y * stride, row);
-        SV_HIP(hipMemcpyAsync(c->img[k].p, dst, n, hipMemcpyHostToDevice, c->stream));
+        SV_HIP(c->copy(c->img[k].p, dst, n, hipMemcpyHostToDevice, c->stream));
     }
     SV_HIP(c->stats.ensure(nimg * (2 * nb + 256) * sizeof(uint32_t)));
     uint32_t* d = c->stats.as<uint32_t>();
@@ -1014,29 +1014,34 @@ int sv_frame_stats(sv_ctx* c, const uint8_t* img0, const uint8_t* img1, int H, i
 }
 
 // One select pass over the context stream (a batch of a.narr arrays): hist [narr][kMaxRanks]
-// [2048] and counts [narr][2] back on the host.
+// [2048] (null: not wanted) and counts [narr][2] (null: not wanted) back on the host.
 static int select_pass(sv_ctx* c, sv::SelectArgs& a, uint32_t* hist_host, unsigned long long* counts_host) {
     // device: [kSelBatch][copies][kMaxRanks][2048] accumulators | [kSelBatch] count slots |
-    // folded hist [narr][kMaxRanks][2048] | counts [narr][2].  The accumulator regions are
+    // counts [narr][2] | folded hist [narr][kMaxRanks][2048].  The accumulator regions are
     // laid out for the largest batch whatever narr is: the folds leave them zeroed, and a
     // smaller batch's outputs must never land where a larger batch accumulates
     const size_t na = (size_t)(a.narr > 0 ? a.narr : 1);
     const size_t hb = (size_t)sv::kMaxRanks * 2048 * sizeof(uint32_t);
     const size_t ab = (size_t)sv::kSelBatch * sv::kHistCopies * hb;
     const size_t cb = (size_t)sv::kSelBatch * sv::kCountSlots * 16 * sizeof(unsigned long long);
-    const size_t ob = na * hb + na * 16;
+    const size_t ob = na * 16 + na * hb;
     SV_HIP(c->sel.ensure_zeroed(ab + cb + ob));
     uint8_t* base = c->sel.as<uint8_t>();
     a.ghist = reinterpret_cast<uint32_t*>(base);
     a.counts = reinterpret_cast<unsigned long long*>(base + ab);
-    a.hist_out = reinterpret_cast<uint32_t*>(base + ab + cb);
-    a.counts_out = reinterpret_cast<unsigned long long*>(base + ab + cb + na * hb);
+    a.counts_out = reinterpret_cast<unsigned long long*>(base + ab + cb);
+    a.hist_out = reinterpret_cast<uint32_t*>(base + ab + cb + na * 16);
     SV_LAUNCH(c, SV_K_SELECT, c->stream, sv::launch_select_hist(a, c->stream));
+    // one copy, and only of what the host reads: the counts, then the histograms up to the last
+    // bin of the last rank of the last array this pass fills (pass digits have `bits` bits; a
+    // count-only call reads no histogram)
+    const size_t nr = hist_host ? (size_t)(a.nranks > 0 ? a.nranks : 1) : 0;
+    const size_t used = nr ? (na - 1) * hb + ((nr - 1) * 2048 + ((size_t)1 << a.bits)) * sizeof(uint32_t) : 0;
     SV_HIP(c->hout.ensure(ob));
-    SV_HIP(hipMemcpyAsync(c->hout.p, a.hist_out, ob, hipMemcpyDeviceToHost, c->stream));
+    SV_HIP(c->copy(c->hout.p, a.counts_out, na * 16 + used, hipMemcpyDeviceToHost, c->stream));
     SV_HIP(hipStreamSynchronize(c->stream));
-    std::memcpy(hist_host, c->hout.p, na * hb);
-    if (counts_host) std::memcpy(counts_host, c->hout.as<uint8_t>() + na * hb, na * 16);
+    if (counts_host) std::memcpy(counts_host, c->hout.p, na * 16);
+    if (used) std::memcpy(hist_host, c->hout.as<uint8_t>() + na * 16, used);
     return 0;
 }
 
@@ -1081,7 +1086,7 @@ static int select_batch(sv_ctx* c, const float* d_x, int64_t n, int64_t x_stride
         for (int y = 0; y < narr; ++y)
             for (int r = 0; r < sv::kMaxRanks; ++r) a.prefix[y][r] = p == 0 ? 0u : prefix[y][r];
         if (n > 0) {
-            int rc = select_pass(c, a, h.data(), p == 0 ? cnt.data() : nullptr);
+            int rc = select_pass(c, a, nranks > 0 ? h.data() : nullptr, p == 0 ? cnt.data() : nullptr);
             if (rc) return rc;
         }
         if (p == 0) {
@@ -1136,7 +1141,7 @@ int sv_select_ranks_batch(sv_ctx* c, const float* d_x, int64_t n, int64_t x_stri
 int sv_affine_f32_dev(sv_ctx* c, const float* d_x, int64_t n, int mode, float fa, float fb, float fc, float fd,
                       double ds, double doff, float* d_out, void* stream) {
     SV_ENTER(c);
-    if (!d_x || !d_out || n < 0 || mode < 0 || mode > 2) return fail(SV_EINVAL, "bad affine arguments");
+    if (!d_x || !d_out || n < 0 || mode < 0 || mode > sv::AFF_NORM_CLIP255) return fail(SV_EINVAL, "bad affine arguments");
     hipStream_t s = pick(c, stream);
     sv::AffineArgs a{};
     a.x = d_x;
@@ -1221,14 +1226,14 @@ int sv_bilateral_f32_dev(sv_ctx* c, const float* d_src, int H, int W, int radius
     }
     if (radius > 0) {
         float* d_lut = reinterpret_cast<float*>(c->fuse.as<char>() + kFuseLutOff);
-        SV_HIP(hipMemcpyAsync(d_lut, lut, sv::kBilateralLut * sizeof(float), hipMemcpyHostToDevice, s));
+        SV_HIP(c->copy(d_lut, lut, sv::kBilateralLut * sizeof(float), hipMemcpyHostToDevice, s));
         SV_HIP(hipStreamSynchronize(s));   // the caller's table may go once this call returns
         a.lut = d_lut;
     }
     SV_LAUNCH(c, SV_K_FUSE, s, sv::launch_bilateral_f32(a, space_w, s));
     if (minmax_out) {
         uint32_t slots[sv::kFuseSlots * sv::kFuseSlotStride], w[4];
-        SV_HIP(hipMemcpyAsync(slots, a.stats, sizeof(slots), hipMemcpyDeviceToHost, s));
+        SV_HIP(c->copy(slots, a.stats, sizeof(slots), hipMemcpyDeviceToHost, s));
         SV_HIP(hipStreamSynchronize(s));
         sv::fuse_stats_fold(slots, w);
         minmax_out[0] = sv::fuse_stat_min(w);
@@ -1278,7 +1283,7 @@ int sv_fuse_blend_dev(sv_ctx* c, const sv_fuse_args* g, float* d_fused, sv_fuse_
     SV_LAUNCH(c, SV_K_FUSE, s, sv::launch_fuse_blend(a, s));
     if (stats) {
         uint32_t slots[sv::kFuseSlots * sv::kFuseSlotStride], w[4];
-        SV_HIP(hipMemcpyAsync(slots, a.stats, sizeof(slots), hipMemcpyDeviceToHost, s));
+        SV_HIP(c->copy(slots, a.stats, sizeof(slots), hipMemcpyDeviceToHost, s));
         SV_HIP(hipStreamSynchronize(s));
         sv::fuse_stats_fold(slots, w);
         stats->min = sv::fuse_stat_min(w);
@@ -1466,12 +1471,21 @@ int sv_flow_depth_dev(sv_ctx* c, const float* d_flow, int H, int W, const double
     SV_LAUNCH(c, SV_K_FLOW, s, sv::launch_flow_depth(a, s));
     if (minmax_out) {
         uint32_t slots[sv::kFuseSlots * sv::kFuseSlotStride], w[4];
-        SV_HIP(hipMemcpyAsync(slots, a.stats, sizeof(slots), hipMemcpyDeviceToHost, s));
+        SV_HIP(c->copy(slots, a.stats, sizeof(slots), hipMemcpyDeviceToHost, s));
         SV_HIP(hipStreamSynchronize(s));
         sv::fuse_stats_fold(slots, w);
         minmax_out[0] = sv::fuse_stat_min(w);
         minmax_out[1] = sv::fuse_stat_max(w);
     }
+    return 0;
+}
+
+int sv_flow_grid_dev(sv_ctx* c, const float* d_flow, int H, int W, int step, float* d_out, void* stream) {
+    SV_ENTER(c);
+    if (!d_flow || !d_out || H <= 0 || W <= 0 || step < 1) return fail(SV_EINVAL, "bad flow-grid arguments");
+    if ((((uintptr_t)d_flow) | ((uintptr_t)d_out)) & 7) return fail(SV_EINVAL, "flow grid: pointers must be 8-byte aligned");
+    hipStream_t s = pick(c, stream);
+    SV_LAUNCH(c, SV_K_FLOW, s, sv::launch_flow_grid(d_flow, H, W, step, d_out, s));
     return 0;
 }
 
@@ -1532,7 +1546,7 @@ int sv_filter_speckles(sv_ctx* c, int16_t* img, int H, int W, int new_val, int m
     SV_HIP(c->hin.ensure(bytes));
     std::memcpy(c->hin.p, img, bytes);
     c->scratch_written(c->d16.p);
-    SV_HIP(hipMemcpyAsync(c->d16.p, c->hin.p, bytes, hipMemcpyHostToDevice, c->stream));
+    SV_HIP(c->copy(c->d16.p, c->hin.p, bytes, hipMemcpyHostToDevice, c->stream));
     const int rc = enqueue_speckles(c, c->d16.as<int16_t>(), H, W, W, new_val, max_speckle_size, max_diff, c->stream);
     if (rc) return rc;
     Out o[] = {{img, c->d16.p, bytes}};

@@ -36,10 +36,10 @@ int depth_map_shard(sv_ctx* c, const uint8_t* left, const uint8_t* right, int f0
         uint8_t* stage = c->hin.as<uint8_t>() + k * nf * fin;
         std::memcpy(stage, src[k] + (size_t)f0 * fin, nf * fin);
         if (channels == 1) {
-            SV_HIP(hipMemcpyAsync(c->gray[k].p, stage, nf * fin, hipMemcpyHostToDevice, c->stream));
+            SV_HIP(c->copy(c->gray[k].p, stage, nf * fin, hipMemcpyHostToDevice, c->stream));
         } else {
             SV_HIP(c->img[k].ensure(nf * fin));
-            SV_HIP(hipMemcpyAsync(c->img[k].p, stage, nf * fin, hipMemcpyHostToDevice, c->stream));
+            SV_HIP(c->copy(c->img[k].p, stage, nf * fin, hipMemcpyHostToDevice, c->stream));
             // contiguous frames: the shard's BGR stack is one (nf*H) x W image, one launch
             SV_LAUNCH(c, SV_K_GRAY, c->stream,
                       sv::launch_gray(c->img[k].as<uint8_t>(), nf * H, W, W * channels, c->gray[k].as<uint8_t>(),
@@ -477,8 +477,8 @@ int rows_impl(sv_ctx* const* ctxs, sv_comm* const* comms, int ndev, const uint8_
             ProfScope ps(c, SV_K_H2D, c->stream);
             const size_t off = (size_t)rows[k].in0 * pitch, nb = (size_t)(rows[k].in1 - rows[k].in0) * pitch;
             for (int i = 0; i < 2; ++i)
-                SV_HIP(hipMemcpyAsync(c->img[i].as<uint8_t>() + (size_t)SV_BAND_MARGIN * pitch,
-                                      (i ? d_right[0] : d_left[0]) + off, nb, hipMemcpyHostToDevice, c->stream));
+                SV_HIP(c->copy(c->img[i].as<uint8_t>() + (size_t)SV_BAND_MARGIN * pitch,
+                               (i ? d_right[0] : d_left[0]) + off, nb, hipMemcpyHostToDevice, c->stream));
             ps.done();
         }
         SV_HIP(hipSetDevice(root->device));

@@ -204,6 +204,21 @@ struct sv_ctx {
     bool cur_open = false;
     EvPair region{};            // sv_profile_region_begin/end (separate from `cur`: kernels
     bool region_open = false;   // launched inside a region keep their own pairs)
+    // sv_copy_counters: bytes and calls of the host-to-device, then the device-to-host copies
+    // this context has issued (plain host counters, written under `mu`)
+    uint64_t copy_ctr[4] = {};
+
+    // hipMemcpyAsync of the library, counted when it crosses the host/device boundary
+    hipError_t copy(void* dst, const void* src, size_t bytes, hipMemcpyKind kind, hipStream_t s) {
+        if (kind == hipMemcpyHostToDevice) {
+            copy_ctr[0] += bytes;
+            copy_ctr[1] += 1;
+        } else if (kind == hipMemcpyDeviceToHost) {
+            copy_ctr[2] += bytes;
+            copy_ctr[3] += 1;
+        }
+        return hipMemcpyAsync(dst, src, bytes, kind, s);
+    }
 
     hipEvent_t get_event() {
         if (!pool.empty()) {

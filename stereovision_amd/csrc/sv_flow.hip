@@ -253,9 +253,33 @@ __global__ __launch_bounds__(256) void k_flow_depth(FlowDepthArgs a) {
     fold_stats(kmin_inv, kmax, 0, 0, red, a.stats);
 }
 
+// The flow at the ego-motion grid (fused_depth_map.py:1447-1455): out[j * nx + i] = flow[y0 + j
+// step][x0 + i step], y0 = x0 = step / 2.  One lane per point, one 8-byte load and store each.
+__global__ __launch_bounds__(256) void k_flow_grid(const float2* __restrict__ flow, int W, int step, int nx, int np,
+                                                   float2* __restrict__ out) {
+    const int p = blockIdx.x * 256 + threadIdx.x;
+    if (p >= np) return;
+    const int j = p / nx, i = p - j * nx;
+    const int y = step / 2 + j * step, x = step / 2 + i * step;
+    out[p] = flow[(size_t)y * W + x];
+}
+
 dim3 tile_grid(int H, int W) { return dim3((W + kTW - 1) / kTW, (H + kTH - 1) / kTH); }
 
 }  // namespace
+
+int flow_grid_points(int n, int step) { return n > step / 2 ? (n - step / 2 + step - 1) / step : 0; }
+
+int launch_flow_grid(const float* flow, int H, int W, int step, float* out, hipStream_t s) {
+    if (H <= 0 || W <= 0 || step < 1) return (int)hipErrorInvalidValue;
+    const int ny = flow_grid_points(H, step), nx = flow_grid_points(W, step);
+    const long long np = (long long)ny * nx;
+    if (np == 0) return 0;
+    if (np > 0x7fffffffll) return (int)hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_flow_grid, dim3((unsigned)((np + 255) / 256)), dim3(256), 0, s,
+                       reinterpret_cast<const float2*>(flow), W, step, nx, (int)np, reinterpret_cast<float2*>(out));
+    return (int)hipGetLastError();
+}
 
 int launch_fb_u8_f32(const uint8_t* src, int H, int W, int pitch, float* dst, hipStream_t s) {
     if (H <= 0 || W <= 0 || pitch < W) return (int)hipErrorInvalidValue;

@@ -192,7 +192,15 @@ struct SelectArgs {
 constexpr int kCountSlots = 32;   // blocks add their counts into slot blockIdx % 32 (128 B apart)
 int launch_select_hist(const SelectArgs& a, hipStream_t s);
 
-enum AffineMode { AFF_F32 = 0, AFF_F64 = 1, AFF_FILL = 2 };
+enum AffineMode {
+    AFF_F32 = 0,
+    AFF_F64 = 1,
+    AFF_FILL = 2,
+    // the frame loop's normalisations (fused_depth_map.py:2749-2759, :2793-2811)
+    AFF_F32_INV = 3,          // 255 - AFF_F32
+    AFF_CLIP255_INV = 4,      // 255 - clip(x * 255, 0, 255)
+    AFF_NORM_CLIP255 = 5      // clip(((x - fa) / fb) * 255, 0, 255)
+};
 struct AffineArgs {
     const float* x;
     float* out;
@@ -313,6 +321,10 @@ int launch_fb_polyexp(const FbPolyArgs& a, hipStream_t s);
 int launch_fb_update_matrices(const FbUpdateArgs& a, hipStream_t s);
 int launch_fb_blur_solve(const FbSolveArgs& a, hipStream_t s);
 int launch_flow_depth(const FlowDepthArgs& a, hipStream_t s);
+// The points step / 2, step / 2 + step, ... below n; the gather of an H x W x 2 flow (8-byte
+// aligned) at that grid into out [ny * nx][2].
+int flow_grid_points(int n, int step);
+int launch_flow_grid(const float* flow, int H, int W, int step, float* out, hipStream_t s);
 
 // SGBM-3WAY mode (sv_sgbm.hip).
 struct SgbmArgs {

@@ -12,7 +12,9 @@
 //                    with the reference's boolean masks (x > 0, confidence > 0.7) applied
 //                    as predicates, so the masked array is never materialised.
 //  * k_affine_f32    the elementwise epilogues of those functions, in NumPy's precision
-//                    (float32 ops in order, or float64 scale/offset then astype(float32)).
+//                    (float32 ops in order, or float64 scale/offset then astype(float32)), and
+//                    the frame loop's normalisations of the flow depth and of the MiDaS map
+//                    without stereo (fused_depth_map.py:2749-2759, :2793-2811).
 // All HBM-bound: one read of the image / map per pass.
 #include "sv_internal.h"
 
@@ -303,6 +305,9 @@ __global__ __launch_bounds__(256) void k_select_fold(const SelectArgs a) {
     }
 }
 
+// np.clip(v, 0, 255) of a float32: a NaN stays a NaN
+__device__ __forceinline__ float clip255(float v) { return v < 0.f ? 0.f : (v > 255.f ? 255.f : v); }
+
 __global__ __launch_bounds__(256) void k_affine_f32(AffineArgs a) {
     const size_t stride = (size_t)gridDim.x * 256;
     for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < a.n; i += stride) {
@@ -313,6 +318,14 @@ __global__ __launch_bounds__(256) void k_affine_f32(AffineArgs a) {
             y = a.fc + nrm * a.fd;
         } else if (a.mode == AFF_F64) {   // astype(float32) of (float64(x) * s + o)
             y = (float)((double)x * a.ds + a.doff);
+        } else if (a.mode == AFF_F32_INV) {        // 255.0 - AFF_F32 (:2796-2804)
+            const float nrm = (x - a.fa) / a.fb;
+            y = 255.0f - (a.fc + nrm * a.fd);
+        } else if (a.mode == AFF_CLIP255_INV) {    // 255.0 - np.clip(x * 255.0, 0, 255) (:2809-2811)
+            y = 255.0f - clip255(x * 255.0f);
+        } else if (a.mode == AFF_NORM_CLIP255) {   // np.clip(((x - a) / b) * 255.0, 0, 255) (:2754-2759)
+            const float nrm = (x - a.fa) / a.fb;
+            y = clip255(nrm * 255.0f);
         } else {                          // np.full_like(x, c)
             y = a.fc;
         }

@@ -49,7 +49,7 @@ EXPORTED = [
     "sv_frame_stats_batch_dev", "sv_select_count_batch", "sv_select_ranks_batch", "sv_event_record",
     "sv_stream_wait_event", "sv_post_m16_dev", "sv_gauss_blur_f32_dev", "sv_bilateral_f32_dev",
     "sv_fuse_blend_dev", "sv_farneback_flow_dev", "sv_fb_polyexp_dev", "sv_fb_update_matrices_dev",
-    "sv_fb_blur_solve_dev", "sv_flow_depth_dev",
+    "sv_fb_blur_solve_dev", "sv_flow_depth_dev", "sv_flow_grid_dev", "sv_copy_counters",
 ]
 BAND_MARGIN = 8   # SV_BAND_MARGIN: spare rows around a band-only input buffer
 COMM_ID_BYTES = 128
@@ -267,6 +267,8 @@ def _declare(lib):
         "sv_fb_blur_solve_dev": ([_vp, _vp, _c_int, _c_int, _c_int, _vp, _c_int, _vp], _c_int),
         "sv_flow_depth_dev": ([_vp, _vp, _c_int, _c_int, _f64p, _vp, _vp, _c_float, _c_float, _NullableF32,
                                _vp], _c_int),
+        "sv_flow_grid_dev": ([_vp, _vp, _c_int, _c_int, _c_int, _vp, _vp], _c_int),
+        "sv_copy_counters": ([_vp, ctypes.POINTER(ctypes.c_uint64), _c_int], _c_int),
         "sv_sgbm": ([_vp, _u8p, _u8p] + [_c_int] * 14 + [_i16p], _c_int),
         "sv_sgbm_dev": ([_vp, _vp, _vp] + [_c_int] * 13 + [_vp, _c_int, _vp], _c_int),
         "sv_filter_speckles": ([_vp, _i16p] + [_c_int] * 5, _c_int),
@@ -650,6 +652,15 @@ class Engine:
         out = np.empty(shape, dtype)
         _check("sv_copy_to_host", self.lib.sv_copy_to_host(self._h, out.ctypes.data, ptr, out.nbytes, None))
         return out
+
+    def copy_counters(self, reset: bool = False) -> dict:
+        """Host <-> device traffic of this context since its creation or the last reset
+        (sv_copy_counters): every copy the library issued for it, the scalar read-backs inside
+        the `_dev` entry points included."""
+        out = (ctypes.c_uint64 * 4)()
+        _check("sv_copy_counters", self.lib.sv_copy_counters(self._h, out, 1 if reset else 0))
+        return {"h2d_bytes": int(out[0]), "h2d_calls": int(out[1]), "d2h_bytes": int(out[2]),
+                "d2h_calls": int(out[3])}
 
     def median5(self, a: np.ndarray) -> np.ndarray:
         a = np.ascontiguousarray(a, np.float32)
@@ -1193,6 +1204,13 @@ class Engine:
             self._h, d_flow, int(H), int(W), Hm, d_depth, d_stable or None, np.float32(alpha),
             np.float32(1.0 - float(alpha)), mm, stream or None))
         return (mm[0], mm[1]) if minmax else None
+
+    def flow_grid_dev(self, d_flow: int, H: int, W: int, step: int, d_out: int, stream: int = 0):
+        """sv_flow_grid_dev: d_out[j * nx + i] = flow[step // 2 + j * step, step // 2 + i * step]
+        of an H x W x 2 device flow (d_out: ny * nx * 2 floats); returns (ny, nx)."""
+        _check("sv_flow_grid_dev", self.lib.sv_flow_grid_dev(self._h, d_flow, int(H), int(W), int(step), d_out,
+                                                             stream or None))
+        return len(range(step // 2, H, step)), len(range(step // 2, W, step))
 
     def rectify_pair(self, dmaps, left, right):
         """Both remaps of apply_stereo_rectification with device-resident maps

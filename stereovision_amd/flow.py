@@ -9,7 +9,8 @@ and ``stable_depth`` resident on the device.
 The kernels (csrc/sv_flow.hip) evaluate no exp and invert no matrix: the pyramid's Gaussian
 coefficients, the polynomial expansion's tables and the four entries of its inverse moment
 matrix are built here in float64 ("Optical flow").  The ego-motion homography is
-a host step in float64 on the step-16 grid of the flow (about 880 points at 633 x 356).
+a host step in float64 on the step-16 grid of the flow (about 880 points at 633 x 356); only
+the grid's flow vectors come back from the device (``k_flow_grid``), never the whole flow.
 """
 from __future__ import annotations
 
@@ -326,7 +327,8 @@ class OpticalFlowDepthEstimator:
     """fused_depth_map.py:1263-1501 on the MI355X engine: Farneback flow between consecutive
     frames, a RANSAC homography for the camera's own motion, the residual flow turned into
     1 / (m + 0.5), an exponential average and a bilateral filter.  Returns a float32 map, or
-    None on the first frame, on a size change, on a static scene and on any error."""
+    None on the first frame, on a size change, on a static scene and on any error.
+    ``step_dev`` is the same call on a gray frame that is already on the device."""
 
     FLOW_ARGS = (0.5, 3, 15, 3, 5, 1.2, 0)             # :1361-1370
 
@@ -340,7 +342,7 @@ class OpticalFlowDepthEstimator:
         self._shape = None          # (H, W) of the previous gray frame on the device
         self._bufs = {}
         self._buf_shape = None
-        self._cur = 0               # index of the gray buffer that holds the previous frame
+        self._prev = 0              # device pointer of the previous gray frame (own buffer or the caller's)
         self._have_stable = False
         print("[INFO] optical-flow depth estimator initialised")
         print(f"       inlier threshold: {min_inliers}, motion timeout: {motion_timeout} s")
@@ -350,7 +352,7 @@ class OpticalFlowDepthEstimator:
     def prev_gray(self):
         if self._shape is None:
             return None
-        return self._eng.to_host(self._bufs["gray"][self._cur], self._shape, np.uint8)
+        return self._eng.to_host(self._prev, self._shape, np.uint8)
 
     @prev_gray.setter
     def prev_gray(self, value):
@@ -390,23 +392,43 @@ class OpticalFlowDepthEstimator:
     def _alloc(self, H, W):
         self._free()
         n, a = H * W, self._eng.dev_alloc
+        points = len(range(GRID_STEP // 2, H, GRID_STEP)) * len(range(GRID_STEP // 2, W, GRID_STEP))
         self._bufs = {"gray": [a(n), a(n)], "flow": a(8 * n), "depth": a(4 * n), "stable": a(4 * n),
-                      "out": a(4 * n)}
+                      "out": a(4 * n), "grid": a(max(8 * points, 8))}
         self._buf_shape = (H, W)
 
-    def _upload_gray(self, frame, slot):
-        eng = self._eng
+    def _load_gray(self, frame, d_gray):
+        """The device pointer of the new gray frame: the caller's (step_dev), or the own buffer
+        that does not hold the previous frame, filled from the host frame."""
+        if d_gray:
+            return d_gray
+        eng, g = self._eng, self._bufs["gray"]
+        dst = g[1] if self._prev == g[0] else g[0]
         H, W = frame.shape[:2]
         if frame.ndim == 3:
             d_bgr = eng.upload("ofd_bgr", frame)
-            eng.gray_dev(d_bgr, H, W, W * 3, self._bufs["gray"][slot])
+            eng.gray_dev(d_bgr, H, W, W * 3, dst)
         else:
-            eng.to_device(self._bufs["gray"][slot], frame)
+            eng.to_device(dst, frame)
+        return dst
 
     # -- the call ---------------------------------------------------------------------------
     def __call__(self, frame):
         try:
             return self._step(frame)
+        except Exception:
+            return None
+
+    def step_dev(self, d_gray: int, H: int, W: int):
+        """__call__ on a dense gray uint8 H x W frame in device memory: the same state machine
+        and results, with no upload of the frame and no download of the map.  Returns the
+        device pointer of the float32 H x W map (the estimator's buffer, valid until its next
+        call), or None where __call__ returns None.  The frame at d_gray becomes the previous
+        frame: the caller leaves it unchanged until the estimator's next call has returned."""
+        try:
+            if not d_gray or int(H) <= 0 or int(W) <= 0:
+                return None
+            return self._advance((int(H), int(W)), None, int(d_gray))
         except Exception:
             return None
 
@@ -416,9 +438,13 @@ class OpticalFlowDepthEstimator:
         frame = np.ascontiguousarray(frame)
         if frame.dtype != np.uint8 or not (frame.ndim == 2 or (frame.ndim == 3 and frame.shape[2] == 3)):
             return None
+        shape = frame.shape[:2]
+        d_out = self._advance(shape, frame, 0)
+        return None if d_out is None else self._eng.to_host(d_out, shape, np.float32)
+
+    def _advance(self, shape, frame, d_gray):
         if self._eng is None:
             self._eng = get_engine()
-        shape = frame.shape[:2]
         if self._shape is None or shape != self._shape:      # the first frame, or a size change
             if self._shape is not None:
                 self._have_stable = False
@@ -426,24 +452,21 @@ class OpticalFlowDepthEstimator:
             if self._buf_shape != shape:
                 self._have_stable = False
                 self._alloc(*shape)
-            self._cur = 0
-            self._upload_gray(frame, 0)
+            self._prev = self._load_gray(frame, d_gray)
             self._shape = shape
             return None
         H, W = shape
         eng, b = self._eng, self._bufs
-        nxt = self._cur ^ 1
-        self._upload_gray(frame, nxt)
+        nxt = self._load_gray(frame, d_gray)
         current_time = time.time()
         self.camera_moving = (current_time - self.last_move_time) < self.motion_timeout
         try:
             ego_valid, Hm = False, None
             if H >= 16 and W >= 16:
-                farneback_flow_dev(eng, b["gray"][self._cur], b["gray"][nxt], H, W, *self.FLOW_ARGS,
-                                   d_flow=b["flow"])
+                farneback_flow_dev(eng, self._prev, nxt, H, W, *self.FLOW_ARGS, d_flow=b["flow"])
                 ego_valid, Hm = self._estimate_ego_motion(H, W)
         finally:
-            self._cur = nxt                              # the new frame is the previous one from now on
+            self._prev = nxt                             # the new frame is the previous one from now on
         if ego_valid:
             self.last_move_time = current_time
             self.camera_moving = True
@@ -455,12 +478,12 @@ class OpticalFlowDepthEstimator:
                 eng.bilateral_f32_dev(b["depth"], H, W, 0, None, None, 0.0, d_dst_f32=b["stable"])   # a copy
                 self._have_stable = True
             _fusion.bilateral_filter_dev(eng, b["depth"], H, W, mn, mx, 9, 75, 75, b["out"])
-            return eng.to_host(b["out"], (H, W), np.float32)
+            return b["out"]
         if self.camera_moving and self._have_stable:
             # the stable map lies in (0, 2], so the clipped range of the radius-0 pass is its range
             mn, mx = eng.bilateral_f32_dev(b["stable"], H, W, 0, None, None, 0.0, minmax=True)
             _fusion.bilateral_filter_dev(eng, b["stable"], H, W, mn, mx, 9, 75, 75, b["out"])
-            return eng.to_host(b["out"], (H, W), np.float32)
+            return b["out"]
         return None
 
     def _estimate_ego_motion(self, H, W):
@@ -471,8 +494,10 @@ class OpticalFlowDepthEstimator:
         points = np.vstack((x_coords.ravel(), y_coords.ravel())).T.astype(np.float32)
         if len(points) == 0 or len(points) < self.min_inliers * 2:
             return False, None
-        flow = self._eng.to_host(self._bufs["flow"], (H, W, 2), np.float32)
-        next_points = points + flow[y_coords.ravel(), x_coords.ravel()]
+        # the flow at the grid alone crosses to the host (k_flow_grid), in the order of `points`
+        self._eng.flow_grid_dev(self._bufs["flow"], H, W, GRID_STEP, self._bufs["grid"])
+        flow_vectors = self._eng.to_host(self._bufs["grid"], (len(points), 2), np.float32)
+        next_points = points + flow_vectors
         Hm, mask = find_homography_ransac(points, next_points, 3.0, 2000, 0.995)
         if Hm is None or mask is None or np.sum(mask) < self.min_inliers:
             return False, None

@@ -15,6 +15,10 @@ settings (``FUSION_*``, ``fusion_params``, read at call time) and return value a
 blend, Gaussian fill weight, bilateral filter, quantisation and colormap run on the GPU
 (``fusion.fuse_maps``).
 
+``process_frame(frame_left, frame_right, stereo_calib, midas)`` runs the whole frame body
+(fused_depth_map.py:2483-2842) through ``frame.FusionFramePipeline``, the maps staying on the
+device between the stages.
+
 ``OpticalFlowDepthEstimator`` (fused_depth_map.py:1263-1501), the producer of
 ``flow_depth_normalized``, is ``flow.OpticalFlowDepthEstimator``: Farneback flow, residual depth
 and the bilateral filter on the GPU, the RANSAC homography on the host.
@@ -122,6 +126,50 @@ def _valid(use, m) -> bool:
     return bool(use) and m is not None and np.size(m) > 0
 
 
+def fuse_settings() -> dict:
+    """fusion.fuse_maps' parameters from this module's settings, read at call time."""
+    fp = fusion_params
+    return dict(
+        stereo_weight=fp["stereo_weight"], midas_fill_weight=fp["midas_fill_weight"],
+        flow_fill_weight=fp["flow_fill_weight"], stereo_conf_threshold=fp["stereo_conf_threshold"],
+        flow_hole_threshold=fp["flow_hole_threshold"], use_midas_fill=FUSION_METHODS["use_midas_fill"],
+        use_flow_fill=FUSION_METHODS["use_flow_fill"], midas_blend_radius=FUSION_SMOOTHING["midas_blend_radius"],
+        bilateral_d=FUSION_SMOOTHING["fusion_bilateral_d"],
+        bilateral_sigma=FUSION_SMOOTHING["fusion_bilateral_sigma"])
+
+
+def fuse_mode(info: dict) -> dict:
+    """fuse_maps' info with the mode parts (:1629, :1650, :1662, :1668, :1678, :1684) and the mode
+    text: a fill is named when it changed a pixel."""
+    fp = fusion_params
+    mode_parts = []
+    if info["base"] == _fusion.BASE_STEREO:
+        mode_parts.append(f"Stereo\u00d7{fp['stereo_weight']:.1f}")
+        if info["n_midas"] > 0:
+            mode_parts.append(f"MiDaS_fill\u00d7{fp['midas_fill_weight']:.1f}")
+    elif info["base"] == _fusion.BASE_MIDAS:
+        mode_parts.append("MiDaS_base")
+    else:
+        mode_parts.append("Flow_base")
+    if info["n_hole"] > 0:
+        mode_parts.append(f"Flow_fill\u00d7{fp['flow_fill_weight']:.1f}")
+    mode_text = " + ".join(mode_parts) if mode_parts else "NO DATA"
+    return dict(info, mode_parts=mode_parts, mode_text=mode_text)
+
+
+def annotate_fused(fused_colormap, info: dict, valid_flow: bool, camera_moving) -> None:
+    """The overlays of fuse_depth_maps (:1702-1716) on the host colormap."""
+    min_val, max_val = info["range"]
+    w = fused_colormap.shape[1]
+    colormap.put_text(fused_colormap, f"FUSED: {info['mode_text']}", (10, 30), scale=0.65)
+    colormap.put_text(fused_colormap, f"Range: {min_val:.0f}-{max_val:.0f}", (10, 55), scale=0.5,
+                      color=(0, 255, 255), thickness=1)
+    if valid_flow:     # (camera_moving holds whenever the flow map is valid)
+        motion_text = "CAM MOVING" if camera_moving else "STATIC"
+        colormap.put_text(fused_colormap, motion_text, (w - 150, 30), scale=0.5,
+                          color=(0, 255, 0) if camera_moving else (0, 0, 255), thickness=1)
+
+
 def fuse_depth_maps(stereo_depth, stereo_conf, midas_depth_calibrated, midas_conf,
                     flow_depth_normalized, camera_moving, use_stereo=True, use_midas=True,
                     use_flow=True):
@@ -135,45 +183,41 @@ def fuse_depth_maps(stereo_depth, stereo_conf, midas_depth_calibrated, midas_con
     valid_flow = _valid(use_flow, flow_depth_normalized) and bool(camera_moving)
     if not (valid_stereo or valid_midas or valid_flow):
         return None
-    fp = fusion_params
     res = _fusion.fuse_maps(
         stereo_depth if valid_stereo else None,
         stereo_conf if valid_stereo else None,
         midas_depth_calibrated if valid_midas else None,
         flow_depth_normalized if valid_flow else None,
-        cmap=colormap.table("jet"), engine=get_engine(),
-        stereo_weight=fp["stereo_weight"], midas_fill_weight=fp["midas_fill_weight"],
-        flow_fill_weight=fp["flow_fill_weight"], stereo_conf_threshold=fp["stereo_conf_threshold"],
-        flow_hole_threshold=fp["flow_hole_threshold"], use_midas_fill=FUSION_METHODS["use_midas_fill"],
-        use_flow_fill=FUSION_METHODS["use_flow_fill"], midas_blend_radius=FUSION_SMOOTHING["midas_blend_radius"],
-        bilateral_d=FUSION_SMOOTHING["fusion_bilateral_d"],
-        bilateral_sigma=FUSION_SMOOTHING["fusion_bilateral_sigma"])
+        cmap=colormap.table("jet"), engine=get_engine(), **fuse_settings())
     fused_uint8, fused_colormap, info = res
-    # the mode parts (:1629, :1650, :1662, :1668, :1678, :1684): a fill is named when it changed a pixel
-    mode_parts = []
-    if info["base"] == _fusion.BASE_STEREO:
-        mode_parts.append(f"Stereo\u00d7{fp['stereo_weight']:.1f}")
-        if info["n_midas"] > 0:
-            mode_parts.append(f"MiDaS_fill\u00d7{fp['midas_fill_weight']:.1f}")
-    elif info["base"] == _fusion.BASE_MIDAS:
-        mode_parts.append("MiDaS_base")
-    else:
-        mode_parts.append("Flow_base")
-    if info["n_hole"] > 0:
-        mode_parts.append(f"Flow_fill\u00d7{fp['flow_fill_weight']:.1f}")
-    mode_text = " + ".join(mode_parts) if mode_parts else "NO DATA"
-    min_val, max_val = info["range"]
-    info = dict(info, mode_parts=mode_parts, mode_text=mode_text)
+    info = fuse_mode(info)
     last_fuse_info = info
-    w = fused_uint8.shape[1]
-    colormap.put_text(fused_colormap, f"FUSED: {mode_text}", (10, 30), scale=0.65)
-    colormap.put_text(fused_colormap, f"Range: {min_val:.0f}-{max_val:.0f}", (10, 55), scale=0.5,
-                      color=(0, 255, 255), thickness=1)
-    if valid_flow:     # (camera_moving holds whenever the flow map is valid)
-        motion_text = "CAM MOVING" if camera_moving else "STATIC"
-        colormap.put_text(fused_colormap, motion_text, (w - 150, 30), scale=0.5,
-                          color=(0, 255, 0) if camera_moving else (0, 0, 255), thickness=1)
+    annotate_fused(fused_colormap, info, valid_flow, camera_moving)
     return fused_uint8, fused_colormap
+
+
+_frame_pipelines: dict = {}      # id(calibration) -> (calibration, FusionFramePipeline)
+
+
+def process_frame(frame_left, frame_right, stereo_calib=None, midas=None, **pipeline_args):
+    """One iteration of the frame loop (fused_depth_map.py:2483-2842) with every map resident on
+    the device: ``frame.FusionFramePipeline.step`` on a pipeline kept per calibration object
+    (``pipeline_args`` configure it when it is first made).  Returns the step's FrameResult."""
+    from .frame import FusionFramePipeline
+    entry = _frame_pipelines.get(id(stereo_calib))
+    if entry is None or entry[0] is not stereo_calib:
+        if entry is not None:
+            entry[1].close()
+        entry = (stereo_calib, FusionFramePipeline(stereo_calib, **pipeline_args))
+        _frame_pipelines[id(stereo_calib)] = entry
+    return entry[1].step(frame_left, frame_right, midas)
+
+
+def frame_pipeline(stereo_calib=None):
+    """The pipeline process_frame keeps for ``stereo_calib`` (None before its first frame): its
+    ``use_stereo`` / ``use_midas`` / ``use_flow`` / ``show_fused`` switches are the loop's USE_*."""
+    entry = _frame_pipelines.get(id(stereo_calib))
+    return entry[1] if entry is not None and entry[0] is stereo_calib else None
 
 
 def warmup(height: int = 356, width: int = 633, processing_scale: float = None) -> None:

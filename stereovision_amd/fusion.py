@@ -40,22 +40,19 @@ from .engine import get_engine
 
 SEL_ALL, SEL_POSITIVE, SEL_MASK_GT = 0, 1, 2
 AFF_F32, AFF_F64, AFF_FILL = 0, 1, 2
+# the frame loop's normalisations (fused_depth_map.py:2749-2759, :2793-2811)
+AFF_F32_INV, AFF_CLIP255_INV, AFF_NORM_CLIP255 = 3, 4, 5
 
 
 # ----------------------------------------------------------------------------------------
 # np.percentile from GPU order statistics
 # ----------------------------------------------------------------------------------------
-def percentile_dev(eng, d_x: int, n: int, q, mask_mode: int = SEL_ALL, d_mask: int = 0,
-                   thr: float = 0.0, dtype=np.float32):
-    """np.percentile(x[mask], q) (method 'linear') of a float32 device array."""
-    sel, nans = eng.select_count(d_x, n, mask_mode, d_mask, thr)
-    if sel + nans == 0:
-        raise IndexError("index -1 is out of bounds for axis 0 with size 0")   # NumPy's error
-    # numpy/lib/_function_base_impl.py: percentile -> _quantile (method 'linear')
+def _quantile_ranks(cnt: int, q, dtype):
+    """numpy/lib/_function_base_impl.py: percentile -> _quantile (method 'linear') up to the
+    indices: (virtual index, previous, next, previous rank, next rank)."""
     qa = np.asanyarray(np.true_divide(q, dtype(100)))
     if np.any(qa < 0) or np.any(qa > 1):
         raise ValueError("Percentiles must be in the range [0, 100]")
-    cnt = sel + nans
     vi = np.asanyarray((cnt - 1) * qa)
     prev = np.asanyarray(np.floor(vi))
     nxt = np.asanyarray(prev + 1)
@@ -69,29 +66,51 @@ def percentile_dev(eng, d_x: int, n: int, q, mask_mode: int = SEL_ALL, d_mask: i
         nxt[below] = 0
     prev = prev.astype(np.intp)
     nxt = nxt.astype(np.intp)
-    if nans:
-        out = np.full(vi.shape, np.nan, dtype)
-        return out[()] if out.ndim == 0 else out
     pr = np.where(prev < 0, cnt - 1, prev).ravel()
     nr = np.where(nxt < 0, cnt - 1, nxt).ravel()
-    ranks = np.unique(np.concatenate([pr, nr]))
+    return vi, prev, nxt, pr, nr
+
+
+def percentiles_dev(eng, d_x: int, n: int, qs, mask_mode: int = SEL_ALL, d_mask: int = 0,
+                    thr: float = 0.0, dtype=np.float32) -> list:
+    """[np.percentile(x[mask], q) for q in qs] (method 'linear') of a float32 device array: one
+    count and the order statistics of every q fetched together (four ranks per select), each q
+    then interpolated on its own with NumPy's dtype rules for that q."""
+    sel, nans = eng.select_count(d_x, n, mask_mode, d_mask, thr)
+    if sel + nans == 0:
+        raise IndexError("index -1 is out of bounds for axis 0 with size 0")   # NumPy's error
+    cnt = sel + nans
+    plans = [_quantile_ranks(cnt, q, dtype) for q in qs]
+    if nans:
+        outs = [np.full(vi.shape, np.nan, dtype) for vi, *_ in plans]
+        return [o[()] if o.ndim == 0 else o for o in outs]
+    ranks = np.unique(np.concatenate([np.concatenate([pr, nr]) for *_, pr, nr in plans]))
     vals = {}
     for i in range(0, ranks.size, 4):
         chunk = ranks[i:i + 4]
         for r, v in zip(chunk, eng.select_ranks(d_x, n, chunk, mask_mode, d_mask, thr)):
             vals[int(r)] = v
-    previous = np.array([vals[int(r)] for r in pr], dtype).reshape(vi.shape)
-    nextv = np.array([vals[int(r)] for r in nr], dtype).reshape(vi.shape)
-    gamma = np.asanyarray(vi - prev)
-    gamma = np.asanyarray(gamma, dtype=vi.dtype)
-    # _lerp
-    diff_b_a = np.subtract(nextv, previous)
-    res = np.asanyarray(np.add(previous, diff_b_a * gamma))
-    np.subtract(nextv, diff_b_a * (1 - gamma), out=res, where=gamma >= 0.5, casting="unsafe",
-                dtype=type(res.dtype))
-    if res.ndim == 0:
-        res = res[()]
-    return res
+    out = []
+    for vi, prev, nxt, pr, nr in plans:
+        previous = np.array([vals[int(r)] for r in pr], dtype).reshape(vi.shape)
+        nextv = np.array([vals[int(r)] for r in nr], dtype).reshape(vi.shape)
+        gamma = np.asanyarray(vi - prev)
+        gamma = np.asanyarray(gamma, dtype=vi.dtype)
+        # _lerp
+        diff_b_a = np.subtract(nextv, previous)
+        res = np.asanyarray(np.add(previous, diff_b_a * gamma))
+        np.subtract(nextv, diff_b_a * (1 - gamma), out=res, where=gamma >= 0.5, casting="unsafe",
+                    dtype=type(res.dtype))
+        if res.ndim == 0:
+            res = res[()]
+        out.append(res)
+    return out
+
+
+def percentile_dev(eng, d_x: int, n: int, q, mask_mode: int = SEL_ALL, d_mask: int = 0,
+                   thr: float = 0.0, dtype=np.float32):
+    """np.percentile(x[mask], q) (method 'linear') of a float32 device array."""
+    return percentiles_dev(eng, d_x, n, [q], mask_mode, d_mask, thr, dtype)[0]
 
 
 def percentile(x: np.ndarray, q, positive: bool = False):
@@ -215,6 +234,43 @@ def _affine(eng, d_x: int, shape, mode: int, **kw) -> np.ndarray:
     return eng.to_host(d_out, shape, np.float32)
 
 
+def _calibrate_plan(eng, d_md: int, d_sd: int, d_cf: int, n: int):
+    """The scalars of calibrate_midas_to_stereo (:1222-1254) from the device maps: (affine mode,
+    its parameters)."""
+    sel, nans = eng.select_count(d_sd, n, SEL_MASK_GT, d_cf, 0.7)
+    if sel + nans < 100:                       # np.sum(reliable_mask) < 100
+        midas_min, midas_max = percentiles_dev(eng, d_md, n, [5, 95])
+        stereo_min, stereo_max = percentiles_dev(eng, d_sd, n, [5, 95])
+        if (midas_max - midas_min) < 1e-6:
+            c = np.full((1,), (stereo_min + stereo_max) / 2.0, np.float32)[0]
+            return AFF_FILL, dict(fc=c)
+        den = midas_max - midas_min + 1e-8
+        rng = stereo_max - stereo_min
+        return AFF_F32, dict(fa=midas_min, fb=den, fc=stereo_min, fd=rng)
+    stereo_min, stereo_max = percentile_dev(eng, d_sd, n, [10, 90], SEL_MASK_GT, d_cf, 0.7)
+    midas_min, midas_max = percentile_dev(eng, d_md, n, [10, 90], SEL_MASK_GT, d_cf, 0.7)
+    if (midas_max - midas_min) < 1e-6:
+        scale = 1.0
+    else:
+        scale = (stereo_max - stereo_min) / (midas_max - midas_min + 1e-8)
+    offset = stereo_min - midas_min * scale
+    return AFF_F64, dict(ds=float(scale), doff=float(offset))
+
+
+def calibrate_midas_to_stereo_dev(eng, d_midas: int, mH: int, mW: int, d_stereo: int, d_conf: int, H: int,
+                                  W: int, d_out: int, d_resized: int = 0) -> None:
+    """calibrate_midas_to_stereo on device maps: d_midas (mH x mW) is resized into d_resized
+    (H x W floats) when its size differs (:1215-1217); the calibrated map goes to d_out (which
+    may be d_resized).  The percentiles' order statistics come back to the host, no map does."""
+    if (mH, mW) != (H, W):
+        if not d_resized:
+            raise ValueError("calibrate_midas_to_stereo_dev: a buffer for the resized map is needed")
+        eng.resize_f32_dev(d_midas, mH, mW, d_resized, H, W)
+        d_midas = d_resized
+    mode, kw = _calibrate_plan(eng, d_midas, d_stereo, d_conf, H * W)
+    eng.affine_f32_dev(d_midas, H * W, mode, d_out, **kw)
+
+
 def calibrate_midas_to_stereo(midas_depth, stereo_disparity, stereo_confidence):
     """fused_depth_map.py:1169-1257 (percentile calibration of a relative depth map to the
     stereo disparity range) with the reductions and the epilogue on the GPU."""
@@ -232,26 +288,27 @@ def calibrate_midas_to_stereo(midas_depth, stereo_disparity, stereo_confidence):
     n = H * W
     d_sd = eng.upload("cal_disp", sd)
     d_cf = eng.upload("cal_conf", _f32_map(stereo_confidence, "stereo_confidence"))
-    sel, nans = eng.select_count(d_sd, n, SEL_MASK_GT, d_cf, 0.7)
-    if sel + nans < 100:                       # np.sum(reliable_mask) < 100
-        midas_min = percentile_dev(eng, d_md, n, 5)
-        midas_max = percentile_dev(eng, d_md, n, 95)
-        stereo_min = percentile_dev(eng, d_sd, n, 5)
-        stereo_max = percentile_dev(eng, d_sd, n, 95)
-        if (midas_max - midas_min) < 1e-6:
-            c = np.full((1,), (stereo_min + stereo_max) / 2.0, np.float32)[0]
-            return _affine(eng, d_md, (H, W), AFF_FILL, fc=c)
-        den = midas_max - midas_min + 1e-8
-        rng = stereo_max - stereo_min
-        return _affine(eng, d_md, (H, W), AFF_F32, fa=midas_min, fb=den, fc=stereo_min, fd=rng)
-    stereo_min, stereo_max = percentile_dev(eng, d_sd, n, [10, 90], SEL_MASK_GT, d_cf, 0.7)
-    midas_min, midas_max = percentile_dev(eng, d_md, n, [10, 90], SEL_MASK_GT, d_cf, 0.7)
-    if (midas_max - midas_min) < 1e-6:
-        scale = 1.0
+    mode, kw = _calibrate_plan(eng, d_md, d_sd, d_cf, n)
+    return _affine(eng, d_md, (H, W), mode, **kw)
+
+
+def minmax_normalize_dev(eng, d_x: int, n: int, d_out: int):
+    """The MiDaS normalisation without stereo (fused_depth_map.py:2749-2759) of a float32 device
+    map: clip(((x - min) / (max - min + 1e-8)) * 255.0, 0, 255), zeros when max <= min + 1e-6,
+    float32 throughout.  min and max are order statistics 0 and n - 1 of the radix select (a
+    NaN in the map makes both NaN, as np.min / np.max do).  Returns (min, max)."""
+    sel, nans = eng.select_count(d_x, n)
+    if sel + nans == 0:
+        raise ValueError("zero-size array to reduction operation minimum which has no identity")
+    if nans:
+        min_val = max_val = np.float32(np.nan)
     else:
-        scale = (stereo_max - stereo_min) / (midas_max - midas_min + 1e-8)
-    offset = stereo_min - midas_min * scale
-    return _affine(eng, d_md, (H, W), AFF_F64, ds=float(scale), doff=float(offset))
+        min_val, max_val = (np.float32(v) for v in eng.select_ranks(d_x, n, [0, n - 1]))
+    if max_val > min_val + 1e-6:
+        eng.affine_f32_dev(d_x, n, AFF_NORM_CLIP255, d_out, fa=min_val, fb=max_val - min_val + 1e-8)
+    else:
+        eng.affine_f32_dev(d_x, n, AFF_FILL, d_out, fc=0.0)
+    return min_val, max_val
 
 
 # ----------------------------------------------------------------------------------------
@@ -444,6 +501,23 @@ def fuse_maps(stereo, conf, midas, flow, *, cmap=None, engine=None, **params):
     return u8, bgr, info
 
 
+def _normalize_plan(eng, d_dm: int, n_dm: int, d_sd: int, n_sd: int):
+    """The scalars of normalize_to_stereo_range (:1523-1552) from the device maps: (affine mode,
+    its parameters)."""
+    sel, _ = eng.select_count(d_sd, n_sd, SEL_POSITIVE)
+    if sel > 0:                                # np.any(stereo_valid)
+        stereo_min, stereo_max = percentiles_dev(eng, d_sd, n_sd, [5, 95], SEL_POSITIVE)
+    else:
+        stereo_min, stereo_max = 0, 255
+    d_min, d_max = percentiles_dev(eng, d_dm, n_dm, [5, 95])
+    if (d_max - d_min) < 1e-6:
+        c = np.full((1,), (stereo_min + stereo_max) / 2.0, np.float32)[0]
+        return AFF_FILL, dict(fc=c)
+    den = d_max - d_min + 1e-8
+    rng = np.float32(stereo_max - stereo_min)
+    return AFF_F32, dict(fa=d_min, fb=den, fc=np.float32(stereo_min), fd=rng)
+
+
 def normalize_to_stereo_range(depth_map, stereo_disparity):
     """fused_depth_map.py:1503-1554 with the reductions and the epilogue on the GPU."""
     if depth_map is None or stereo_disparity is None:
@@ -453,17 +527,19 @@ def normalize_to_stereo_range(depth_map, stereo_disparity):
     dm = _f32_map(depth_map, "depth_map")
     d_sd = eng.upload("nrm_disp", sd)
     d_dm = eng.upload("nrm_depth", dm)
-    sel, _ = eng.select_count(d_sd, sd.size, SEL_POSITIVE)
-    if sel > 0:                                # np.any(stereo_valid)
-        stereo_min = percentile_dev(eng, d_sd, sd.size, 5, SEL_POSITIVE)
-        stereo_max = percentile_dev(eng, d_sd, sd.size, 95, SEL_POSITIVE)
+    mode, kw = _normalize_plan(eng, d_dm, dm.size, d_sd, sd.size)
+    return _affine(eng, d_dm, dm.shape, mode, **kw)
+
+
+def flow_normalize_dev(eng, d_depth: int, n: int, d_stereo_disparity: int, d_out: int) -> None:
+    """The flow normalisation of the frame loop (fused_depth_map.py:2793-2811) on device maps, in
+    one elementwise pass: 255.0 - normalize_to_stereo_range(depth, disparity) with a stereo
+    disparity, 255.0 - clip(depth * 255.0, 0, 255) without one (d_stereo_disparity = 0)."""
+    if not d_stereo_disparity:
+        eng.affine_f32_dev(d_depth, n, AFF_CLIP255_INV, d_out)
+        return
+    mode, kw = _normalize_plan(eng, d_depth, n, d_stereo_disparity, n)
+    if mode == AFF_FILL:                        # 255.0 - np.full_like(x, c), in float32
+        eng.affine_f32_dev(d_depth, n, AFF_FILL, d_out, fc=np.float32(255.0) - np.float32(kw["fc"]))
     else:
-        stereo_min, stereo_max = 0, 255
-    d_min = percentile_dev(eng, d_dm, dm.size, 5)
-    d_max = percentile_dev(eng, d_dm, dm.size, 95)
-    if (d_max - d_min) < 1e-6:
-        c = np.full((1,), (stereo_min + stereo_max) / 2.0, np.float32)[0]
-        return _affine(eng, d_dm, dm.shape, AFF_FILL, fc=c)
-    den = d_max - d_min + 1e-8
-    rng = np.float32(stereo_max - stereo_min)
-    return _affine(eng, d_dm, dm.shape, AFF_F32, fa=d_min, fb=den, fc=np.float32(stereo_min), fd=rng)
+        eng.affine_f32_dev(d_depth, n, AFF_F32_INV, d_out, **kw)
