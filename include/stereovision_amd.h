@@ -111,7 +111,9 @@ enum sv_kernel {
     SV_K_D2H = 17,      /* host-buffer entry points: the outputs' download */
     SV_K_FUSE = 18,     /* fuse_depth_maps: the blend, the Gaussian and the bilateral filter */
     SV_K_FLOW = 19,     /* Farneback optical flow and the flow depth (every launch of sv_flow.hip) */
-    SV_NKERNELS = 20
+    SV_K_FLIP = 20,     /* k_flip_rows: the column mirrors around the right-referenced match */
+    SV_K_REFINE = 21,   /* k_refine: L-R check, curvature test and sub-pixel step of a WTA map */
+    SV_NKERNELS = 22
 };
 
 int sv_version(void);
@@ -468,6 +470,54 @@ int sv_sgbm_dev(sv_ctx* ctx, const uint8_t* d_left, const uint8_t* d_right, int 
 int sv_filter_speckles(sv_ctx* ctx, int16_t* img, int H, int W, int new_val, int max_speckle_size, int max_diff);
 int sv_filter_speckles_dev(sv_ctx* ctx, int16_t* d_img, int H, int W, int pitch, int new_val,
                            int max_speckle_size, int max_diff, void* stream);
+
+/* ---- refinement of the winner-take-all maps ---------------------------
+ * What cv2.StereoBM adds to its argmin, for the SAD / SSD / HOG maps: a left-right check, a
+ * curvature (texture) test, the parabolic sub-pixel step in the int16 x16 convention and the
+ * speckle filter.  Semantics: tests/sv_refine_oracle.py.  Whole frames only (no row bands, no
+ * batches).  INV = (min_disp - 1) * 16.
+ *
+ * sv_disparity_right_dev: the right-referenced map, defined for every cost as the matcher run
+ * on the column-mirrored pair (right as left) and mirrored back; valid columns
+ * [max(-min_disp, 0), W - max(min_disp + num_disp, 0)), INV elsewhere.
+ *
+ * sv_refine_dev: per pixel of d_disp16 (any int16 map; d_out16 == d_disp16 allowed; the three
+ * maps share out_pitch, in elements): values that are not 16 d with d in the sweep -> INV; with
+ * lr_max_diff >= 0 and a right map, a pixel whose counterpart x - d lies in the image, is valid
+ * there and differs by more than lr_max_diff -> INV; min_curvature > 0: cm + cp - 2 c0 <
+ * min_curvature -> INV (the window costs at d - 1, d + 1 and d, mirrored at the ends of the
+ * sweep); subpixel: d * 16 plus the parabola's vertex offset in [-8, 8]; speckle_window > 0:
+ * sv_filter_speckles_dev(out, INV, speckle_window, 16 * speckle_range).  HOG takes the L-R
+ * check and the speckle filter only.  SV_EINVAL before any launch: null pointers (the right
+ * map may be NULL), pitch or out_pitch < W, d_disp16_right == d_out16, the int16 range rule,
+ * an even win, cost = SV_COST_SGBM, min_curvature < 0, and subpixel or min_curvature > 0 with
+ * SV_COST_HOG.
+ *
+ * sv_disparity_refined[_dev]: left match, right match (only when lr_max_diff >= 0), refine,
+ * speckle.  sv_refine_plan: LDS bytes of k_refine's staged form for (num_disp, win) and whether
+ * a launch with the costs takes it (*lds_form = 1) or the global-tap form (0). */
+typedef struct sv_refine_params {
+    int lr_max_diff;      /* < 0: no left-right check */
+    int min_curvature;    /* 0: no curvature test */
+    int subpixel;         /* != 0: parabolic sub-pixel step */
+    int speckle_window;   /* <= 0: no speckle filter */
+    int speckle_range;    /* in whole disparities */
+} sv_refine_params;
+int sv_refine_plan(int num_disp, int win, int* lds_bytes, int* lds_form);
+int sv_disparity_right_dev(sv_ctx* ctx, const uint8_t* d_left, const uint8_t* d_right, int H, int W,
+                           int pitch, int min_disp, int num_disp, int win, int cost,
+                           int16_t* d_disp16_right, int out_pitch, void* stream);
+int sv_refine_dev(sv_ctx* ctx, const uint8_t* d_left, const uint8_t* d_right, int H, int W, int pitch,
+                  const int16_t* d_disp16, const int16_t* d_disp16_right, int min_disp, int num_disp,
+                  int win, int cost, const sv_refine_params* params, int16_t* d_out16, int out_pitch,
+                  void* stream);
+int sv_disparity_refined_dev(sv_ctx* ctx, const uint8_t* d_left, const uint8_t* d_right, int H, int W,
+                             int pitch, int min_disp, int num_disp, int win, int cost,
+                             const sv_refine_params* params, int16_t* d_out16, int out_pitch,
+                             void* stream);
+int sv_disparity_refined(sv_ctx* ctx, const uint8_t* left, const uint8_t* right, int H, int W,
+                         int channels, int stride, int min_disp, int num_disp, int win, int cost,
+                         const sv_refine_params* params, int16_t* disp16);
 
 /* ---- reductions around the path ----------------------------
  * Image statistics of detect_camera_occlusion (fused_depth_map.py:131-301) for one image

@@ -118,6 +118,8 @@ struct sv_ctx {
         sg_hsum, sg_c, sg_l, sg_lt, sg_band, sg_rec, cc_parent, cc_size, hist_copies, cmap, bgr;
     DevBuf fuse;   // sv_fuse.hip: the accumulator copies (kFuseStatsBytes), then the bilateral colour table
     DevBuf flow;   // sv_flow.hip: the pyramid images, R0, R1, M and two levels' flow of sv_farneback_flow_dev
+    // sv_refine.hip: the mirrored gray pair, the mirrored match and the right-referenced map
+    DevBuf rf_img[2], rf_map, rf_right;
     uint8_t cmap_host[768] = {};   // BGR table currently in `cmap`
     bool cmap_valid = false;
     // host-buffer frame path: int16 medians come back over PCIe and are expanded on the

@@ -385,6 +385,32 @@ int launch_sgbm(const SgbmArgs& a, int nf, hipStream_t s, hipStream_t aux, hipEv
 int launch_speckles(int16_t* img, int H, int W, int pitch, int newv, int maxsize, int maxdiff, int* parent,
                     int* size, hipStream_t s, int nf = 1, long long fimg = 0);
 
+// Refinement of a winner-take-all map (sv_refine.hip).
+struct RefineArgs {
+    const uint8_t* L;          // gray frames, row pitch `pitch` bytes
+    const uint8_t* R;
+    int H, W, pitch;
+    const int16_t* dl;         // the map to refine (may be `out`)
+    const int16_t* dr;         // right-referenced map, nullable
+    int16_t* out;
+    int mpitch;                // elements: row pitch of dl, dr and out
+    int minD, D, r;
+    int lr_max_diff;           // < 0: no left-right check
+    int min_curv;              // 0: no curvature test
+    int subpixel;
+};
+// k_refine stages the tile's L rows and the R strip it can reach in LDS when both fit
+// kRefineLdsBudget; beyond it the taps read global memory (same arithmetic, same results)
+constexpr int kRefineLdsBudget = 8 * 1024;
+size_t refine_lds_bytes(int num_disp, int win);
+inline bool refine_lds_form(int num_disp, int win) { return refine_lds_bytes(num_disp, win) <= (size_t)kRefineLdsBudget; }
+// cost: COST_SAD or COST_SSD when a.min_curv > 0 or a.subpixel; any cost otherwise (no taps)
+int launch_refine(const RefineArgs& a, int cost, hipStream_t s);
+// Column mirrors: dst[y][x] = src[y][W - 1 - x]; the u8 form mirrors two images in one launch
+int launch_flip_u8(const uint8_t* s0, const uint8_t* s1, uint8_t* d0, uint8_t* d1, int H, int W, int spitch,
+                   int dpitch, hipStream_t s);
+int launch_flip_i16(const int16_t* src, int16_t* dst, int H, int W, int spitch, int dpitch, hipStream_t s);
+
 // Post-processing modes for the median kernel.
 enum PostMode { POST_NONE = 0, POST_DEPTH = 1, POST_SCALED = 2 };
 struct PostParams {

@@ -22,7 +22,7 @@ import numpy as np
 
 from . import colormap
 from . import rectify as _rectify
-from .engine import get_engine, start_warmup
+from .engine import POST_DEPTH, get_engine, start_warmup
 from .preamble import ensure_same_size as _ensure_same_size
 from .preamble import resize_linear as _resize_linear
 from .preamble import to_engine_image
@@ -35,6 +35,9 @@ NUM_DISP = 16 * 20
 WINDOW_SIZE = 7
 # Cost function of the north_star engine that replaces StereoSGBM: "sad" | "ssd" | "hog".
 COST = "sad"
+# engine.RefineParams: run the refinement stage (left-right check, curvature test, sub-pixel step,
+# speckle filter) between the match and the median.  None: the plain path.
+REFINE = None
 
 
 def ensure_same_size(left_img, right_img):
@@ -85,6 +88,12 @@ def create_depth_map(left_img, right_img, stereo_calib=None, min_depth=0.3, max_
             print(f"ERROR: shapes differ after conversion: {gl.shape} vs {gr.shape}")
             gl, gr = _ensure_same_size(gl, gr)
             h, w = gl.shape[:2]
+        if REFINE is not None:   # match, refine, median, post (+ the colormap) on the device
+            depth_final, disparity, _, _, depth_colormap = engine.refined_frame(
+                gl, gr, MIN_DISP, NUM_DISP, WINDOW_SIZE, REFINE, POST_DEPTH, cost=COST,
+                cmap_bgr=colormap.table("turbo"), min_depth=float(min_depth), max_depth=float(max_depth),
+                min_disp_global=MIN_DISP)
+            return depth_final, disparity, depth_colormap
         # applyColorMap(depth_normalized, TURBO) (:937) runs in the same GPU epilogue
         depth_final, disparity, depth_colormap = engine.depth_map_color(
             gl, gr, MIN_DISP, NUM_DISP, WINDOW_SIZE, float(min_depth), float(max_depth),

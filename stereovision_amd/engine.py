@@ -26,7 +26,7 @@ POST_NONE, POST_DEPTH, POST_SCALED = 0, 1, 2
 KERNELS = {"gray": 0, "harris": 1, "hog": 2, "match": 3, "median": 4, "post": 5, "remap": 6,
            "undistort": 7, "resize": 8, "stats": 9, "select": 10, "affine": 11, "sgbm": 12,
            "speckle": 13, "gather": 14, "scatter": 15, "h2d": 16, "d2h": 17, "fuse": 18,
-           "flow": 19}
+           "flow": 19, "flip": 20, "refine": 21}
 
 # Every symbol include/stereovision_amd.h declares (checked by tests/test_capi.py).
 EXPORTED = [
@@ -50,6 +50,8 @@ EXPORTED = [
     "sv_stream_wait_event", "sv_post_m16_dev", "sv_gauss_blur_f32_dev", "sv_bilateral_f32_dev",
     "sv_fuse_blend_dev", "sv_farneback_flow_dev", "sv_fb_polyexp_dev", "sv_fb_update_matrices_dev",
     "sv_fb_blur_solve_dev", "sv_flow_depth_dev", "sv_flow_grid_dev", "sv_copy_counters",
+    "sv_refine_plan", "sv_disparity_right_dev", "sv_refine_dev", "sv_disparity_refined_dev",
+    "sv_disparity_refined",
 ]
 BAND_MARGIN = 8   # SV_BAND_MARGIN: spare rows around a band-only input buffer
 COMM_ID_BYTES = 128
@@ -153,6 +155,43 @@ class FarnebackParams(ctypes.Structure):
                 ("scale_coef", _vp), ("flow_scale", _c_float), ("winsize", _c_int), ("iterations", _c_int),
                 ("poly_n", _c_int), ("poly_g", _vp), ("poly_xg", _vp), ("poly_xxg", _vp),
                 ("ig", ctypes.c_double * 4)]
+
+
+class _RefineParams(ctypes.Structure):
+    """sv_refine_params."""
+    _fields_ = [("lr_max_diff", _c_int), ("min_curvature", _c_int), ("subpixel", _c_int),
+                ("speckle_window", _c_int), ("speckle_range", _c_int)]
+
+
+class RefineParams:
+    """Settings of the refinement stage of a SAD / SSD / HOG map (sv_refine_params):
+    lr_max_diff < 0 switches the left-right check off, min_curvature 0 the curvature test,
+    speckle_window 0 the speckle filter.  HOG maps take the check and the filter only."""
+
+    def __init__(self, lr_max_diff: int = 1, min_curvature: int = 1, subpixel: bool = True,
+                 speckle_window: int = 0, speckle_range: int = 2):
+        self.lr_max_diff = int(lr_max_diff)
+        self.min_curvature = int(min_curvature)
+        self.subpixel = bool(subpixel)
+        self.speckle_window = int(speckle_window)
+        self.speckle_range = int(speckle_range)
+
+    def c_struct(self) -> "_RefineParams":
+        return _RefineParams(self.lr_max_diff, self.min_curvature, 1 if self.subpixel else 0,
+                             self.speckle_window, self.speckle_range)
+
+    def __repr__(self):
+        return (f"RefineParams(lr_max_diff={self.lr_max_diff}, min_curvature={self.min_curvature}, "
+                f"subpixel={self.subpixel}, speckle_window={self.speckle_window}, "
+                f"speckle_range={self.speckle_range})")
+
+
+def _refine_params(params) -> "_RefineParams":
+    if params is None:
+        params = RefineParams()
+    if not isinstance(params, RefineParams):
+        raise TypeError(f"RefineParams expected, got {type(params).__name__}")
+    return params.c_struct()
 
 
 def map_out(mode: int = POST_NONE, disparity: int = 0, out_a: int = 0, out_u8: int = 0, out_b: int = 0,
@@ -269,6 +308,14 @@ def _declare(lib):
                                _vp], _c_int),
         "sv_flow_grid_dev": ([_vp, _vp, _c_int, _c_int, _c_int, _vp, _vp], _c_int),
         "sv_copy_counters": ([_vp, ctypes.POINTER(ctypes.c_uint64), _c_int], _c_int),
+        "sv_refine_plan": ([_c_int, _c_int, ctypes.POINTER(_c_int), ctypes.POINTER(_c_int)], _c_int),
+        "sv_disparity_right_dev": ([_vp, _vp, _vp] + [_c_int] * 7 + [_vp, _c_int, _vp], _c_int),
+        "sv_refine_dev": ([_vp, _vp, _vp, _c_int, _c_int, _c_int, _vp, _vp, _c_int, _c_int, _c_int, _c_int,
+                           ctypes.POINTER(_RefineParams), _vp, _c_int, _vp], _c_int),
+        "sv_disparity_refined_dev": ([_vp, _vp, _vp] + [_c_int] * 7 + [ctypes.POINTER(_RefineParams), _vp,
+                                                                      _c_int, _vp], _c_int),
+        "sv_disparity_refined": ([_vp, _u8p, _u8p] + [_c_int] * 8 + [ctypes.POINTER(_RefineParams), _i16p],
+                                 _c_int),
         "sv_sgbm": ([_vp, _u8p, _u8p] + [_c_int] * 14 + [_i16p], _c_int),
         "sv_sgbm_dev": ([_vp, _vp, _vp] + [_c_int] * 13 + [_vp, _c_int, _vp], _c_int),
         "sv_filter_speckles": ([_vp, _i16p] + [_c_int] * 5, _c_int),
@@ -359,6 +406,16 @@ def plan(num_disp: int, win: int, cost: str | int = "sad") -> dict:
     return {"dpl": dpl.value, "lpg": lpg.value, "lds_bytes": lds.value}
 
 
+def refine_plan(num_disp: int, win: int) -> dict:
+    """k_refine's plan for (num_disp, win): the LDS bytes of its staged form and whether a
+    launch that needs the window costs takes it ("lds") or reads its taps from global memory
+    ("global")."""
+    lds, form = _c_int(), _c_int()
+    _check("sv_refine_plan", load_library().sv_refine_plan(int(num_disp), int(win), ctypes.byref(lds),
+                                                            ctypes.byref(form)))
+    return {"lds_bytes": lds.value, "form": "lds" if form.value else "global"}
+
+
 def _cost(cost) -> int:
     if isinstance(cost, str):
         try:
@@ -426,6 +483,7 @@ class Engine:
         # call, 2.0k vs 2.9k with 4 in flight): opt-in with SV_REGISTER_OUTPUTS=1
         self._noreg = os.environ.get("SV_REGISTER_OUTPUTS", "0") != "1"
         self._out_lock = threading.Lock()
+        self._refine_lock = threading.Lock()   # refined_frame's scratch: one frame at a time
 
     # -- lifetime -------------------------------------------------------------------
     def close(self):
@@ -616,6 +674,118 @@ class Engine:
         _check("sv_filter_speckles_dev", self.lib.sv_filter_speckles_dev(
             self._h, d_img, H, W, pitch, int(new_val), int(max_speckle_size), int(max_diff),
             stream or None))
+
+    # -- refinement of the SAD / SSD / HOG maps ---------------------------------
+    def _gray_pair_dev(self, left, right):
+        """Upload a gray pair into this engine's scratch -> (d_left, d_right, H, W)."""
+        left, H, W, C = _image(left)
+        right, H2, W2, C2 = _image(right)
+        if (H, W, C) != (H2, W2, C2):
+            raise ValueError("left/right shapes differ")
+        if C != 1:
+            raise ValueError("a gray H x W pair expected")
+        return self.upload("refine_l", left), self.upload("refine_r", right), H, W
+
+    def disparity_right_dev(self, d_left: int, d_right: int, H: int, W: int, pitch: int, min_disp: int,
+                            num_disp: int, win: int, cost, d_out16: int, out_pitch: int, stream: int = 0):
+        """The right-referenced int16 x16 map: the matcher on the column-mirrored pair, mirrored
+        back."""
+        _check("sv_disparity_right_dev", self.lib.sv_disparity_right_dev(
+            self._h, d_left, d_right, H, W, pitch, int(min_disp), int(num_disp), int(win), _cost(cost),
+            d_out16, out_pitch, stream or None))
+
+    def disparity_right(self, left, right, min_disp: int, num_disp: int, win: int, cost="sad") -> np.ndarray:
+        dl, dr, H, W = self._gray_pair_dev(left, right)
+        d_out = self.scratch("refine_right", 2 * H * W)
+        self.disparity_right_dev(dl, dr, H, W, W, min_disp, num_disp, win, cost, d_out, W)
+        return self.to_host(d_out, (H, W), np.int16)
+
+    def refine_dev(self, d_left: int, d_right: int, H: int, W: int, pitch: int, d_disp16: int,
+                   d_disp16_right: int, min_disp: int, num_disp: int, win: int, cost, params,
+                   d_out16: int, out_pitch: int, stream: int = 0):
+        """sv_refine_dev: L-R check, curvature test, sub-pixel step and speckle filter of an int16
+        x16 map (d_disp16_right 0: no check; d_out16 may be d_disp16; the maps share out_pitch)."""
+        p = _refine_params(params)
+        _check("sv_refine_dev", self.lib.sv_refine_dev(
+            self._h, d_left, d_right, H, W, pitch, d_disp16, d_disp16_right or None, int(min_disp),
+            int(num_disp), int(win), _cost(cost), ctypes.byref(p), d_out16, out_pitch, stream or None))
+
+    def refine(self, left, right, disp16, min_disp: int, num_disp: int, win: int, cost="sad", params=None,
+               disp16_right=None) -> np.ndarray:
+        """Refine a host int16 x16 map of the gray pair (a matcher's or any other)."""
+        dl, dr, H, W = self._gray_pair_dev(left, right)
+        m = np.ascontiguousarray(disp16, np.int16)
+        if m.shape != (H, W):
+            raise ValueError(f"map shape {m.shape} != {(H, W)}")
+        d_m = self.upload("refine_map", m)
+        d_r = 0
+        if disp16_right is not None:
+            mr = np.ascontiguousarray(disp16_right, np.int16)
+            if mr.shape != (H, W):
+                raise ValueError(f"right map shape {mr.shape} != {(H, W)}")
+            d_r = self.upload("refine_right", mr)
+        self.refine_dev(dl, dr, H, W, W, d_m, d_r, min_disp, num_disp, win, cost, params, d_m, W)
+        return self.to_host(d_m, (H, W), np.int16)
+
+    def disparity_refined_dev(self, d_left: int, d_right: int, H: int, W: int, pitch: int, min_disp: int,
+                              num_disp: int, win: int, cost, params, d_out16: int, out_pitch: int,
+                              stream: int = 0):
+        """Left match, right match (lr_max_diff >= 0), refine and speckle filter in one call."""
+        p = _refine_params(params)
+        _check("sv_disparity_refined_dev", self.lib.sv_disparity_refined_dev(
+            self._h, d_left, d_right, H, W, pitch, int(min_disp), int(num_disp), int(win), _cost(cost),
+            ctypes.byref(p), d_out16, out_pitch, stream or None))
+
+    def disparity_refined(self, left, right, min_disp: int, num_disp: int, win: int, cost="sad",
+                          params=None) -> np.ndarray:
+        """The refined int16 x16 map of a host pair (HxW gray or HxWx3 BGR)."""
+        left, H, W, C = _image(left)
+        right, H2, W2, C2 = _image(right)
+        if (H, W, C) != (H2, W2, C2):
+            raise ValueError("left/right shapes differ")
+        p = _refine_params(params)
+        d16 = np.empty((H, W), np.int16)
+        _check("sv_disparity_refined", self.lib.sv_disparity_refined(
+            self._h, left, right, H, W, C, W * C, int(min_disp), int(num_disp), int(win), _cost(cost),
+            ctypes.byref(p), d16))
+        return d16
+
+    def refined_frame(self, left, right, min_disp: int, num_disp: int, win: int, params, mode: int,
+                      cost="sad", cmap_bgr=None, min_depth=0.0, max_depth=0.0, min_disp_global=0.0):
+        """The drop-ins' frame body with the refinement stage: match, refine, median, post on a
+        host pair (HxW gray or HxWx3 BGR) -> (out_a, disparity, out_u8, out_b or None, colormap or
+        None) of POST_DEPTH / POST_SCALED.  The refined map holds sub-pixel values, so the median
+        stage looks its outputs up in the checked, full table (the form SGBM maps take)."""
+        if mode not in (POST_DEPTH, POST_SCALED):
+            raise ValueError("refined_frame needs POST_DEPTH or POST_SCALED")
+        left, H, W, C = _image(left)
+        right, H2, W2, C2 = _image(right)
+        if (H, W, C) != (H2, W2, C2):
+            raise ValueError("left/right shapes differ")
+        p = _refine_params(params)   # (a wrong type fails before anything is uploaded)
+        n = H * W
+        with self._refine_lock:
+            d_l, d_r = self.upload("rfr_l", left), self.upload("rfr_r", right)
+            if C == 3:
+                d_gl, d_gr = self.scratch("rfr_gl", n), self.scratch("rfr_gr", n)
+                self.gray_dev(d_l, H, W, 3 * W, d_gl)
+                self.gray_dev(d_r, H, W, 3 * W, d_gr)
+                d_l, d_r = d_gl, d_gr
+            d16 = self.scratch("rfr_d16", 2 * n)
+            _check("sv_disparity_refined_dev", self.lib.sv_disparity_refined_dev(
+                self._h, d_l, d_r, H, W, W, int(min_disp), int(num_disp), int(win), _cost(cost),
+                ctypes.byref(p), d16, W, None))
+            scaled = mode == POST_SCALED
+            d_disp, d_a, d_u8 = self.scratch("rfr_disp", 4 * n), self.scratch("rfr_a", 4 * n), self.scratch("rfr_u8", n)
+            d_b = self.scratch("rfr_b", 4 * n) if scaled else 0
+            d_bgr = self.scratch("rfr_bgr", 3 * n) if cmap_bgr is not None else 0
+            out = map_out(mode, d_disp, d_a, d_u8, d_b, bgr=d_bgr, cmap=cmap_bgr, min_depth=min_depth,
+                          max_depth=max_depth, min_disp_global=min_disp_global)
+            self.median_rows_dev(d16, H, W, 0, H, out, min_disp, num_disp, "sgbm")
+            return (self.to_host(d_a, (H, W), np.float32), self.to_host(d_disp, (H, W), np.float32),
+                    self.to_host(d_u8, (H, W), np.uint8),
+                    self.to_host(d_b, (H, W), np.float32) if scaled else None,
+                    self.to_host(d_bgr, (H, W, 3), np.uint8) if d_bgr else None)
 
     def disparity_rows(self, left, right, min_disp: int, num_disp: int, win: int, row0: int,
                        row1: int, cost="sad", out: np.ndarray | None = None) -> np.ndarray:

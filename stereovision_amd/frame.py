@@ -116,7 +116,7 @@ class FusionFramePipeline:
     def __init__(self, stereo_calib=None, *, use_rectify=True, min_disp=None, num_disp=None,
                  window_size=None, cost=None, engine=None, outputs=("fused_u8", "fused_colormap"),
                  occlusion_check_interval=2, occlusion_hysteresis_frames=5, occlusion_threshold=0.45,
-                 min_inliers=15, motion_timeout=1.5):
+                 min_inliers=15, motion_timeout=1.5, refine=None):
         outputs = tuple(outputs)
         unknown = [n for n in outputs if n not in OUTPUT_NAMES]
         if unknown:
@@ -126,6 +126,7 @@ class FusionFramePipeline:
         self.stereo_calib = stereo_calib
         self.use_rectify = bool(use_rectify)
         self.min_disp, self.num_disp, self.window_size, self.cost = min_disp, num_disp, window_size, cost
+        self.refine = refine        # engine.RefineParams; None: fused_depth_map.REFINE at each step
         self.outputs = outputs
         self.occlusion_threshold = occlusion_threshold
         self.use_midas = True
@@ -350,7 +351,15 @@ class FusionFramePipeline:
         try:
             out = map_out(POST_SCALED, m["stereo_disparity"], m["stereo_depth"], d_u8, m["stereo_conf"], bgr=d_bgr,
                           cmap=colormap.table("jet") if d_bgr else None)
-            eng.depth_map_batch_ex(d_gl, d_gr, 1, H, W, W, H * W, min_disp, num_disp, win, cost, STAGE_ALL, 0, out)
+            from . import fused_depth_map as FDM
+            refine = FDM.REFINE if self.refine is None else self.refine
+            if refine is not None:   # match, refine, then the median over the checked, full table
+                d16 = self._buf("st_d16", 2 * n)
+                eng.disparity_refined_dev(d_gl, d_gr, H, W, W, min_disp, num_disp, win, cost, refine, d16, W)
+                eng.median_rows_dev(d16, H, W, 0, H, out, min_disp, num_disp, "sgbm")
+            else:
+                eng.depth_map_batch_ex(d_gl, d_gr, 1, H, W, W, H * W, min_disp, num_disp, win, cost, STAGE_ALL, 0,
+                                       out)
             ok = True
         except EngineUnavailable:
             raise

@@ -43,7 +43,7 @@ from . import fusion as _fusion
 from . import rectify as _rectify
 from .fusion import (calibrate_midas_to_stereo, detect_camera_occlusion,  # noqa: F401
                      normalize_to_stereo_range)
-from .engine import get_engine, start_warmup
+from .engine import POST_SCALED, get_engine, start_warmup
 from .flow import OpticalFlowDepthEstimator  # noqa: F401
 from .preamble import ensure_same_size, to_engine_image
 
@@ -54,6 +54,10 @@ MIN_DISP_BASE = 0
 NUM_DISP_BASE = 16 * 20
 WINDOW_SIZE_BASE = 7
 COST = "sad"
+# engine.RefineParams: run the refinement stage (left-right check, curvature test, sub-pixel step,
+# speckle filter) between the match and the median, so that occluded and flat
+# regions reach fuse_depth_maps as invalid pixels of confidence 0.  None: the plain path.
+REFINE = None
 
 # fuse_depth_maps' settings (fused_depth_map.py:81-116), read at call time
 FUSION_WEIGHTS = {"stereo_base": 0.8, "midas_max_fill": 0.9, "flow_max_fill": 0.5}
@@ -105,6 +109,12 @@ def create_depth_map_stereo_scaled(left_img, right_img, min_disp, num_disp, wind
         gl = engine.gray(gl) if gl.ndim == 3 else gl
         gr = engine.gray(gr) if gr.ndim == 3 else gr
     try:
+        if REFINE is not None:   # match, refine, median, post (+ the colormap) on the device
+            dn, disparity, _, confidence, depth_colormap = engine.refined_frame(
+                gl, gr, int(min_disp), int(num_disp), int(window_size), REFINE, POST_SCALED, cost=COST,
+                cmap_bgr=colormap.table("jet"))
+            colormap.put_text(depth_colormap, f"Scale:{PROCESSING_SCALE:.2f}x Disp:{num_disp}px")
+            return dn, disparity, depth_colormap, confidence
         # applyColorMap(disparity_normalized u8, JET) (:1013) runs in the same GPU epilogue
         dn, disparity, depth_colormap, confidence = engine.stereo_scaled_color(
             gl, gr, int(min_disp), int(num_disp), int(window_size), colormap.table("jet"), cost=COST)
