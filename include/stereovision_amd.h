@@ -139,6 +139,23 @@ void* sv_stream(sv_ctx* ctx);
  * 256-thread block of the matching kernel. */
 int sv_plan(int num_disp, int win, int cost, int* dpl, int* lpg, int* lds_bytes);
 
+/* Which matcher kind sv_disparity_dev / sv_disparity_batch_dev would run for these arguments
+ * (n_frames = 1, frame_stride = 0 for sv_disparity_dev; whole frames are row0 = 0, row1 = H).
+ * Launches nothing and reads no device memory: only the addresses' alignment counts.
+ * mfma: the SSD matrix-core kind takes the call, with xt x-tiles per wave, nt x'-tiles, mb key
+ * index bits, hb rows per block band, and big = 1 when the edge cells are masked by an
+ * accumulator offset (0: by a per-cell select).  mfma_only: no other kind holds this
+ * (num_disp, win) pair's keys, so a call with mfma = 0 (and rows and a matched band to
+ * compute) returns an error.  Returns what the call's own argument checks return (SV_EINVAL,
+ * SV_ERANGE). */
+typedef struct sv_ssd_mfma_info {
+    int mfma, mfma_only;
+    int xt, nt, mb, hb, big;
+} sv_ssd_mfma_info;
+int sv_ssd_mfma_query(const uint8_t* d_left, const uint8_t* d_right, int H, int W, int pitch,
+                      int64_t frame_stride, int n_frames, int min_disp, int num_disp, int win, int cost,
+                      int row0, int row1, int out_pitch, sv_ssd_mfma_info* info);
+
 /* ---- host-memory entry points (drop-in path) ------------------------------------- */
 int sv_gray(sv_ctx* ctx, const uint8_t* bgr, int H, int W, int stride, uint8_t* gray);
 

@@ -180,6 +180,37 @@ int enqueue_sgbm(sv_ctx* c, const uint8_t* L, const uint8_t* R, int H, int W, in
     return 0;
 }
 
+// The fields of a matcher launch that launch_match's choice of kind reads (images, geometry,
+// matched band, rows, batch strides): enqueue_disparity and sv_ssd_mfma_query both fill them
+// here, so the query cannot drift from the launch.  Rows already clamped to [0, H].
+static sv::MatchParams match_geometry(const uint8_t* L, const uint8_t* R, int H, int W, int pitch, int min_disp,
+                                      int num_disp, int win, int cost, int row0, int row1, int16_t* out, int opitch,
+                                      int nf, long long fs_in, long long fs_out) {
+    sv::MatchParams a{};
+    a.L = L;
+    a.R = R;
+    a.H = H;
+    a.W = W;
+    a.pitch = pitch;
+    a.minD = min_disp;
+    a.D = num_disp;
+    a.win = win;
+    a.r = cost == SV_COST_HOG ? 0 : win / 2;
+    int maxd = min_disp + num_disp;
+    a.X0 = maxd > 0 ? maxd : 0;
+    a.X1 = W + (min_disp < 0 ? min_disp : 0);
+    if (a.X1 > W) a.X1 = W;
+    if (a.X1 < a.X0) a.X1 = a.X0;
+    a.row0 = row0;
+    a.row1 = row1;
+    a.out = out;
+    a.opitch = opitch;
+    a.nf = nf < 1 ? 1 : nf;
+    a.fs_in = fs_in;
+    a.fs_out = fs_out;
+    return a;
+}
+
 // Enqueue disparity for rows [row0,row1) of gray device images.
 // nf > 1: a batch of frames, frame z at L/R + z*fs_in bytes and out + z*fs_out elements
 // (one launch over grid.z; HOG: one histogram launch over both images of every frame, then
@@ -202,32 +233,12 @@ int enqueue_disparity(sv_ctx* c, const uint8_t* L, const uint8_t* R, int H, int 
         return enqueue_sgbm(c, L, R, H, W, pitch, min_disp, num_disp, win, sgbm_reference_params(win), out, opitch,
                             s, nf, fs_in, fs_out);
     }
-    sv::MatchParams a{};
-    a.L = L;
-    a.R = R;
-    a.H = H;
-    a.W = W;
-    a.pitch = pitch;
-    a.minD = min_disp;
-    a.D = num_disp;
-    a.win = win;
-    a.r = cost == SV_COST_HOG ? 0 : win / 2;
-    int maxd = min_disp + num_disp;
-    a.X0 = maxd > 0 ? maxd : 0;
-    a.X1 = W + (min_disp < 0 ? min_disp : 0);
-    if (a.X1 > W) a.X1 = W;
-    if (a.X1 < a.X0) a.X1 = a.X0;
-    a.row0 = row0;
-    a.row1 = row1;
+    sv::MatchParams a = match_geometry(L, R, H, W, pitch, min_disp, num_disp, win, cost, row0, row1, out, opitch, nf,
+                                       fs_in, fs_out);
     a.lpg = plan.lpg;
     a.lpg_log2 = plan.lpg == 16 ? 4 : plan.lpg == 32 ? 5 : 6;
     a.dbits = plan.dbits;
     a.pad_key = (uint32_t)((sv::max_cost(win, cost) + 1) << plan.dbits);
-    a.out = out;
-    a.opitch = opitch;
-    a.nf = nf < 1 ? 1 : nf;
-    a.fs_in = fs_in;
-    a.fs_out = fs_out;
     a.fs_hist = 0;
     if (cost == SV_COST_HOG && a.X1 > a.X0) {
         const long long fh = (long long)H * W * 10;   // elements per frame's histograms
@@ -653,6 +664,30 @@ int sv_plan(int num_disp, int win, int cost, int* dpl, int* lpg, int* lds_bytes)
     if (dpl) *dpl = p.dpl;
     if (lpg) *lpg = p.lpg;
     if (lds_bytes) *lds_bytes = (int)sv::match_lds_bytes(p, cost == SV_COST_HOG ? 0 : win / 2, cost);
+    return 0;
+}
+
+int sv_ssd_mfma_query(const uint8_t* d_left, const uint8_t* d_right, int H, int W, int pitch, int64_t frame_stride,
+                      int n_frames, int min_disp, int num_disp, int win, int cost, int row0, int row1, int out_pitch,
+                      sv_ssd_mfma_info* info) {
+    if (!info) return fail(SV_EINVAL, "null info");
+    *info = sv_ssd_mfma_info{};
+    if (check_image(d_left, H, W) || check_image(d_right, H, W)) return fail(SV_EINVAL, "bad disparity arguments");
+    if (pitch < W || out_pitch < W) return fail(SV_EINVAL, "pitch smaller than width");
+    if (n_frames > 1 && frame_stride < (int64_t)pitch * H) return fail(SV_EINVAL, "frame stride smaller than a frame");
+    sv::MatchPlan plan;
+    const int rc = check_match(H, W, min_disp, num_disp, win, cost, &plan);
+    if (rc) return rc;
+    if (cost == SV_COST_SGBM) return 0;
+    if (row0 < 0) row0 = 0;
+    if (row1 > H) row1 = H;
+    const sv::MatchParams a = match_geometry(d_left, d_right, H, W, pitch, min_disp, num_disp, win, cost, row0, row1,
+                                             nullptr, out_pitch, n_frames, frame_stride, 0);
+    info->mfma_only = plan.mfma_only;
+    if (!sv::match_is_ssd_mfma(a, cost)) return 0;
+    if (!sv::ssd_mfma_shape(a, &info->xt, &info->nt, &info->mb, &info->hb, &info->big))
+        return fail(SV_EINVAL, "the matrix-core kind has no shape for this launch");
+    info->mfma = 1;
     return 0;
 }
 

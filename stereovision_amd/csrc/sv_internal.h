@@ -116,6 +116,11 @@ bool ring_ssd(int cost, int win, int num_disp);   // SSD windows 5..9, D <= 256:
 bool ssd_mfma(int cost, int win, int num_disp);
 bool ssd_mfma_fits(const MatchParams& a, int cost);   // + operand alignment, r == win / 2
 int launch_ssd_mfma(const MatchParams& a, hipStream_t s);
+// The shape launch_ssd_mfma runs `a` with (ssd_shape of its window, D and rows): x-tiles per
+// wave, x'-tiles, key index bits, rows per block band, edge masking by accumulator offset
+bool ssd_mfma_shape(const MatchParams& a, int* xt, int* nt, int* mb, int* hb, int* big);
+// Whether launch_match hands `a` to the matrix-core kind (its own test; nothing is launched)
+bool match_is_ssd_mfma(const MatchParams& a, int cost);
 long long ring_split_elems(int nf, long long fs_out, int row1, int opitch);
 int launch_fill_i16(int16_t* out, int opitch, int H, int W, int16_t v, hipStream_t s);
 

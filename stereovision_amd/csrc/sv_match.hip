@@ -500,6 +500,10 @@ int launch_fill_i16(int16_t* out, int opitch, int H, int W, int16_t v, hipStream
     return (int)hipGetLastError();
 }
 
+bool match_is_ssd_mfma(const MatchParams& a, int cost) {
+    return a.row1 > a.row0 && a.X1 > a.X0 && ssd_mfma_fits(a, cost);
+}
+
 int launch_match(const MatchParams& a, const MatchPlan& p, int cost, hipStream_t s) {
     if (a.row1 <= a.row0) return 0;
     if (a.X1 <= a.X0) {
@@ -510,7 +514,7 @@ int launch_match(const MatchParams& a, const MatchPlan& p, int cost, hipStream_t
         }
         return 0;
     }
-    if (ssd_mfma_fits(a, cost)) return launch_ssd_mfma(a, s);
+    if (match_is_ssd_mfma(a, cost)) return launch_ssd_mfma(a, s);
     if (p.mfma_only) return (int)hipErrorInvalidValue;   // no other kind holds these keys
     // (the ring kind's SAD forms need no place ahead of these two: both concern SSD alone)
     const int e = launch_match_ring(a, cost, s);

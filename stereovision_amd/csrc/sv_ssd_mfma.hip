@@ -525,6 +525,17 @@ bool ssd_mfma_fits(const MatchParams& a, int cost) {
     return ssd_mfma(cost, a.win, a.D) && a.r == a.win / 2 && (al & 3) == 0 && ofits;
 }
 
+bool ssd_mfma_shape(const MatchParams& a, int* xt, int* nt, int* mb, int* hb, int* big) {
+    SsdShape sh;
+    if (!ssd_shape(a.win, a.D, a.row1 - a.row0, &sh)) return false;
+    *xt = sh.xt;
+    *nt = sh.nt;
+    *mb = sh.mb;
+    *hb = sh.hb;
+    *big = sh.big ? 1 : 0;
+    return true;
+}
+
 int launch_ssd_mfma(const MatchParams& a, hipStream_t s) {
     SsdShape sh;
     const int rows = a.row1 - a.row0;

@@ -51,7 +51,7 @@ EXPORTED = [
     "sv_fuse_blend_dev", "sv_farneback_flow_dev", "sv_fb_polyexp_dev", "sv_fb_update_matrices_dev",
     "sv_fb_blur_solve_dev", "sv_flow_depth_dev", "sv_flow_grid_dev", "sv_copy_counters",
     "sv_refine_plan", "sv_disparity_right_dev", "sv_refine_dev", "sv_disparity_refined_dev",
-    "sv_disparity_refined",
+    "sv_disparity_refined", "sv_ssd_mfma_query",
 ]
 BAND_MARGIN = 8   # SV_BAND_MARGIN: spare rows around a band-only input buffer
 COMM_ID_BYTES = 128
@@ -75,6 +75,13 @@ class EngineUnavailable(SVError):
 
 _c_int = ctypes.c_int
 _c_float = ctypes.c_float
+
+
+class SsdMfmaInfo(ctypes.Structure):
+    """sv_ssd_mfma_info (include/stereovision_amd.h)."""
+    _fields_ = [(n, ctypes.c_int) for n in ("mfma", "mfma_only", "xt", "nt", "mb", "hb", "big")]
+
+
 _vp = ctypes.c_void_p
 _u8p = np.ctypeslib.ndpointer(np.uint8, flags="C_CONTIGUOUS")
 _i16p = np.ctypeslib.ndpointer(np.int16, flags="C_CONTIGUOUS")
@@ -228,6 +235,8 @@ def _declare(lib):
         "sv_stream": ([_vp], _vp),
         "sv_plan": ([_c_int, _c_int, _c_int, ctypes.POINTER(_c_int), ctypes.POINTER(_c_int),
                      ctypes.POINTER(_c_int)], _c_int),
+        "sv_ssd_mfma_query": ([_vp, _vp, _c_int, _c_int, _c_int, ctypes.c_int64, _c_int, _c_int, _c_int,
+                               _c_int, _c_int, _c_int, _c_int, _c_int, ctypes.POINTER(SsdMfmaInfo)], _c_int),
         "sv_gray": ([_vp, _u8p, _c_int, _c_int, _c_int, _u8p], _c_int),
         "sv_disparity": ([_vp, _u8p, _u8p, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int,
                           _c_int, _c_int, _i16p, _NullableF32], _c_int),
@@ -404,6 +413,24 @@ def plan(num_disp: int, win: int, cost: str | int = "sad") -> dict:
     _check("sv_plan", load_library().sv_plan(num_disp, win, _cost(cost), ctypes.byref(dpl),
                                               ctypes.byref(lpg), ctypes.byref(lds)))
     return {"dpl": dpl.value, "lpg": lpg.value, "lds_bytes": lds.value}
+
+
+def ssd_mfma_query(d_left: int, d_right: int, H: int, W: int, pitch: int, min_disp: int, num_disp: int,
+                   win: int, cost="ssd", row0: int = 0, row1: int | None = None, out_pitch: int | None = None,
+                   n_frames: int = 1, frame_stride: int = 0) -> dict:
+    """sv_ssd_mfma_query: which matcher kind sv_disparity_dev / sv_disparity_batch_dev would
+    run for these arguments (nothing is launched; of the addresses only the alignment counts).
+    "mfma": the SSD matrix-core kind takes the call, then with its shape "xt", "nt", "mb", "hb",
+    "big"; "mfma_only": no other kind holds this (num_disp, win)."""
+    info = SsdMfmaInfo()
+    _check("sv_ssd_mfma_query", load_library().sv_ssd_mfma_query(
+        d_left, d_right, int(H), int(W), int(pitch), int(frame_stride), int(n_frames), int(min_disp),
+        int(num_disp), int(win), _cost(cost), int(row0), int(H if row1 is None else row1),
+        int(W if out_pitch is None else out_pitch), ctypes.byref(info)))
+    out = {"mfma": bool(info.mfma), "mfma_only": bool(info.mfma_only)}
+    if info.mfma:
+        out.update(xt=info.xt, nt=info.nt, mb=info.mb, hb=info.hb, big=bool(info.big))
+    return out
 
 
 def refine_plan(num_disp: int, win: int) -> dict:
@@ -801,6 +828,13 @@ class Engine:
             self._h, left, right, H, W, C, W * C, int(min_disp), int(num_disp), int(win),
             _cost(cost), int(row0), int(row1), out))
         return out
+
+    def ssd_mfma_query(self, d_left: int, d_right: int, H: int, W: int, pitch: int, min_disp: int,
+                       num_disp: int, win: int, cost="ssd", row0: int = 0, row1: int | None = None,
+                       out_pitch: int | None = None, n_frames: int = 1, frame_stride: int = 0) -> dict:
+        """:func:`ssd_mfma_query` (the answer does not depend on the context)."""
+        return ssd_mfma_query(d_left, d_right, H, W, pitch, min_disp, num_disp, win, cost, row0, row1,
+                              out_pitch, n_frames, frame_stride)
 
     # -- device buffers (torch-free zero-copy use) ------------------------------------
     def dev_alloc(self, nbytes: int) -> int:
