@@ -84,6 +84,8 @@ def max_cost(win: int, cost: int) -> int:
         return win * win * 255
     if cost == COST_SSD:
         return win * win * 255 * 255
+    # HOG: a deliberately loose bound.  A histogram's bins sum to at most win^2 * 191 (the
+    # largest magnitude), so true costs stay below 2 * win^2 * 191.
     return HOG_BINS * win * win * 255
 
 
@@ -145,7 +147,7 @@ def harris(gray: np.ndarray) -> np.ndarray:
 
 def hog_pixel(gray: np.ndarray) -> tuple[np.ndarray, np.ndarray]:
     """Per-pixel (bin, magnitude): unsigned 9-bin orientation by integer tangent tests,
-    magnitude (|gx| + |gy|) >> 3 in [0, 255]."""
+    magnitude (|gx| + |gy|) >> 3 in [0, 191] (|gx| + |gy| <= 1530, at a diagonal step)."""
     gx, gy = sobel(gray)
     mag = ((np.abs(gx) + np.abs(gy)) >> 3).astype(np.int32)
     flip = (gy < 0) | ((gy == 0) & (gx < 0))

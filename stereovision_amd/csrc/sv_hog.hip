@@ -24,8 +24,9 @@ __global__ __launch_bounds__(256) void k_hog_hist(const uint8_t* __restrict__ g,
     __shared__ uint8_t simg[GY_MAX + 2][GX_MAX + 2];
     __shared__ uint16_t sbm[GY_MAX][GX_MAX];             // (bin << 8) | magnitude
     // window-sum records: bins 2k, 2k+1 as the u16 halves of dword k (dword 4's high half
-    // is the zero pad bin 9).  Sums stay below 2^16 (<= 15*15*255), so packed adds and
-    // subtracts never carry or borrow between halves.
+    // is the zero pad bin 9).  Sums stay below 2^16 (<= 15*15*191 = 42,975: the magnitude
+    // (|gx| + |gy|) >> 3 is at most 1530 >> 3), so packed adds and subtracts never carry or
+    // borrow between halves.
     __shared__ uint32_t vrec[GT_H][GX_MAX][5];
     const int x0 = blockIdx.x * GT_W, y0 = row0 + blockIdx.y * GT_H;
     constexpr int nx = GT_W + 2 * r, ny = GT_H + 2 * r;

@@ -448,6 +448,8 @@ int launch_nd(const MatchParams& a, const MatchPlan& p, size_t lds, hipStream_t 
 
 }  // namespace
 
+// HOG: 9 * win^2 * 255 is a deliberately loose bound.  A histogram's bins sum to at most
+// win^2 * 191 (the largest magnitude), so true costs stay below 2 * win^2 * 191.
 uint64_t max_cost(int win, int cost) {
     return cost == COST_SAD ? (uint64_t)win * win * 255
          : cost == COST_SSD ? (uint64_t)win * win * 255 * 255
