@@ -1,7 +1,8 @@
 // sv_capi.cpp — the C ABI (include/stereovision_amd.h) over the gfx950 kernels: errors,
-// contexts, device memory, profiling and the enqueue helpers every entry point shares
-// (sv_ctx.h).  The entry points themselves: sv_capi_dev.cpp (one device), sv_capi_multi.cpp
-// (several devices, RCCL / peer-copy gathers).
+// contexts, device memory, profiling and the enqueue, staging and validation helpers every
+// entry point shares (sv_ctx.h).  The entry points themselves, one file per family: sv_capi_dev.cpp
+// (stereo on device memory), _host (stereo on host buffers), _rectify, _reduce, _fuse (fusion and its
+// optical flow), _refine, and sv_capi_multi.cpp (several devices, RCCL / peer-copy gathers).
 //
 // A context = one device + one HIP stream + grow-only device buffers + pinned staging.
 // Host entry points stage into pinned memory, run the whole chain on the context stream
@@ -30,10 +31,16 @@ int check_image(const void* a, int H, int W) {
     return 0;
 }
 
+int check_channels(int channels) { return channels != 1 && channels != 3 ? fail(SV_EINVAL, "channels must be 1 or 3") : 0; }
+int check_win(int win) { return win < 1 || win > 15 || (win & 1) == 0 ? fail(SV_EINVAL, "win must be odd in [1, 15]") : 0; }
+int check_frame_stride(int n_frames, int64_t frame_stride, int64_t frame) {
+    return n_frames > 1 && frame_stride < frame ? fail(SV_EINVAL, "frame stride smaller than a frame") : 0;
+}
+
 int check_match(int H, int W, int min_disp, int num_disp, int win, int cost, sv::MatchPlan* plan) {
     if (H <= 0 || W <= 0) return fail(SV_EINVAL, "non-positive image size");
     if (num_disp <= 0 || num_disp > 512) return fail(SV_EINVAL, "num_disp must be in [1, 512]");
-    if (win < 1 || win > 15 || (win & 1) == 0) return fail(SV_EINVAL, "win must be odd in [1, 15]");
+    if (check_win(win)) return SV_EINVAL;
     // the int16 x16 map of every cost holds (min_disp - 1) * 16 (invalid) up to
     // (min_disp + num_disp - 1) * 16: beyond [-32768, 32752] both ends would wrap
     if (min_disp < -2047 || min_disp + num_disp - 1 > 2047)
@@ -51,7 +58,6 @@ SgbmParams sgbm_reference_params(int win) {
     return {8 * 3 * win * win, 32 * 3 * win * win, 1, 63, 10, 100, 32};
 }
 
-// Enqueue the whole SGBM-3WAY pipeline for one frame (buffers grown in the context).
 // cv2.filterSpeckles on an int16 device map (speckle stage of SGBM, sv_filter_speckles).
 // nf > 1: a batch of maps, map z at d_img + z*fimg (one launch per stage over grid.z).
 int enqueue_speckles(sv_ctx* c, int16_t* d_img, int H, int W, int pitch, int new_val, int max_speckle_size,
@@ -419,12 +425,19 @@ sv::PostParams map_post(int fmt, void* dst, int d8_base) {
     return pp;
 }
 
+int stage_image(sv_ctx* c, const void* src, int H, size_t row_bytes, size_t stride, size_t hin_off, DevBuf& dst) {
+    const size_t n = (size_t)H * row_bytes;
+    uint8_t* packed = c->hin.as<uint8_t>() + hin_off;
+    pack_rows(packed, static_cast<const uint8_t*>(src), H, row_bytes, stride);
+    SV_HIP(dst.ensure(n));
+    SV_HIP(c->copy(dst.p, packed, n, hipMemcpyHostToDevice, c->stream));
+    return 0;
+}
 
 // Stage two host images (HxW or HxWx3, any stride) into the context's device gray buffers.
 int stage_pair(sv_ctx* c, const uint8_t* left, const uint8_t* right, int H, int W, int channels,
                int stride) {
-    if (check_image(left, H, W) || check_image(right, H, W)) return SV_EINVAL;
-    if (channels != 1 && channels != 3) return fail(SV_EINVAL, "channels must be 1 or 3");
+    if (check_image(left, H, W) || check_image(right, H, W) || check_channels(channels)) return SV_EINVAL;
     const size_t row = (size_t)W * channels;
     if (stride < (int)row) return fail(SV_EINVAL, "stride smaller than a row");
     const size_t n = row * H;
@@ -432,25 +445,12 @@ int stage_pair(sv_ctx* c, const uint8_t* left, const uint8_t* right, int H, int 
     SV_HIP(c->gray[0].ensure((size_t)H * W));
     SV_HIP(c->gray[1].ensure((size_t)H * W));
     const uint8_t* src[2] = {left, right};
-    for (int k = 0; k < 2; ++k) {
-        uint8_t* dst = c->hin.as<uint8_t>() + k * n;
-        if ((size_t)stride == row) {
-            std::memcpy(dst, src[k], n);
-        } else {
-            for (int y = 0; y < H; ++y) std::memcpy(dst + y * row, src[k] + (size_t)y * stride, row);
-        }
-    }
-    if (channels == 1) {
-        SV_HIP(c->copy(c->gray[0].p, c->hin.p, n, hipMemcpyHostToDevice, c->stream));
-        SV_HIP(c->copy(c->gray[1].p, c->hin.as<uint8_t>() + n, n, hipMemcpyHostToDevice, c->stream));
-    } else {
-        SV_HIP(c->img[0].ensure(n));
-        SV_HIP(c->img[1].ensure(n));
-        for (int k = 0; k < 2; ++k) {
-            SV_HIP(c->copy(c->img[k].p, c->hin.as<uint8_t>() + k * n, n, hipMemcpyHostToDevice, c->stream));
+    for (int k = 0; k < 2; ++k) {   // gray images go straight into gray[k]; BGR through img[k] and k_gray
+        if (const int rc = stage_image(c, src[k], H, row, stride, k * n, channels == 1 ? c->gray[k] : c->img[k]))
+            return rc;
+        if (channels == 3)
             SV_LAUNCH(c, SV_K_GRAY, c->stream,
                       sv::launch_gray(c->img[k].as<uint8_t>(), H, W, (int)row, c->gray[k].as<uint8_t>(), c->stream));
-        }
     }
     return 0;
 }
@@ -474,60 +474,6 @@ int collect(sv_ctx* c, const Out* outs, int n) {
         std::memcpy(outs[i].host, c->hout.as<uint8_t>() + off, outs[i].bytes);
         off += (outs[i].bytes + 255) & ~(size_t)255;
     }
-    return 0;
-}
-
-// initUndistortRectifyMap's setup: ir = inv(P[:, :3] * R) with OpenCV's Matx33d product and
-// cofactor inverse (the same operation order as oracle/sv_rectify_oracle.py).
-int make_undistort(const double* K, const double* dist, int ndist, const double* R, const double* P,
-                   int p_cols, int H, int W, sv::UndistortParams* out) {
-    if (!K || H <= 0 || W <= 0) return fail(SV_EINVAL, "bad map arguments");
-    if (H > 32767 || W > 32767) return fail(SV_EINVAL, "map size beyond the int16 coordinate range");
-    if (!(ndist == 0 || ndist == 4 || ndist == 5 || ndist == 8 || ndist == 12 || ndist == 14) ||
-        (ndist > 0 && !dist))
-        return fail(SV_EINVAL, "distCoeffs must have 0, 4, 5, 8, 12 or 14 elements");
-    if (ndist == 14 && (dist[12] != 0.0 || dist[13] != 0.0))
-        return fail(SV_EINVAL, "tilted sensor model (tauX, tauY != 0) is not supported");
-    if (P && p_cols != 3 && p_cols != 4) return fail(SV_EINVAL, "P must be 3x3 or 3x4");
-    double A[9], Rm[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1}, M[9];
-    for (int i = 0; i < 3; ++i)
-        for (int j = 0; j < 3; ++j) A[i * 3 + j] = P ? P[i * p_cols + j] : K[i * 3 + j];
-    if (R) std::memcpy(Rm, R, sizeof(Rm));
-    for (int i = 0; i < 3; ++i)
-        for (int j = 0; j < 3; ++j)
-            M[i * 3 + j] = (A[i * 3 + 0] * Rm[0 * 3 + j] + A[i * 3 + 1] * Rm[1 * 3 + j]) + A[i * 3 + 2] * Rm[2 * 3 + j];
-    auto a = [&](int i, int j) { return M[i * 3 + j]; };
-    const double det = a(0, 0) * (a(1, 1) * a(2, 2) - a(2, 1) * a(1, 2)) -
-                       a(0, 1) * (a(1, 0) * a(2, 2) - a(2, 0) * a(1, 2)) +
-                       a(0, 2) * (a(1, 0) * a(2, 1) - a(2, 0) * a(1, 1));
-    if (det == 0.0) return fail(SV_EINVAL, "singular newCameraMatrix * R");
-    const double d = 1.0 / det;
-    double* b = out->ir;
-    b[0] = (a(1, 1) * a(2, 2) - a(1, 2) * a(2, 1)) * d;
-    b[1] = (a(0, 2) * a(2, 1) - a(0, 1) * a(2, 2)) * d;
-    b[2] = (a(0, 1) * a(1, 2) - a(0, 2) * a(1, 1)) * d;
-    b[3] = (a(1, 2) * a(2, 0) - a(1, 0) * a(2, 2)) * d;
-    b[4] = (a(0, 0) * a(2, 2) - a(0, 2) * a(2, 0)) * d;
-    b[5] = (a(0, 2) * a(1, 0) - a(0, 0) * a(1, 2)) * d;
-    b[6] = (a(1, 0) * a(2, 1) - a(1, 1) * a(2, 0)) * d;
-    b[7] = (a(0, 1) * a(2, 0) - a(0, 0) * a(2, 1)) * d;
-    b[8] = (a(0, 0) * a(1, 1) - a(0, 1) * a(1, 0)) * d;
-    out->fx = K[0];
-    out->fy = K[4];
-    out->u0 = K[2];
-    out->v0 = K[5];
-    for (int i = 0; i < 12; ++i) out->k[i] = i < ndist ? dist[i] : 0.0;
-    out->H = H;
-    out->W = W;
-    return 0;
-}
-
-int check_remap(const void* src, int sH, int sW, int channels, int pitch, const void* map1, int H, int W,
-                const void* dst) {
-    if (!src || !map1 || !dst || sH <= 0 || sW <= 0 || H <= 0 || W <= 0)
-        return fail(SV_EINVAL, "bad remap arguments");
-    if (channels != 1 && channels != 3) return fail(SV_EINVAL, "channels must be 1 or 3");
-    if (pitch < sW * channels) return fail(SV_EINVAL, "source pitch smaller than a row");
     return 0;
 }
 
@@ -674,7 +620,7 @@ int sv_ssd_mfma_query(const uint8_t* d_left, const uint8_t* d_right, int H, int 
     *info = sv_ssd_mfma_info{};
     if (check_image(d_left, H, W) || check_image(d_right, H, W)) return fail(SV_EINVAL, "bad disparity arguments");
     if (pitch < W || out_pitch < W) return fail(SV_EINVAL, "pitch smaller than width");
-    if (n_frames > 1 && frame_stride < (int64_t)pitch * H) return fail(SV_EINVAL, "frame stride smaller than a frame");
+    if (check_frame_stride(n_frames, frame_stride, (int64_t)pitch * H)) return SV_EINVAL;
     sv::MatchPlan plan;
     const int rc = check_match(H, W, min_disp, num_disp, win, cost, &plan);
     if (rc) return rc;

@@ -76,7 +76,7 @@ int sv_multi_gpu_batch(sv_ctx* const* ctxs, int ndev, const uint8_t* left, const
     if (n_frames < 0) return fail(SV_EINVAL, "negative frame count");
     if (n_frames == 0) return 0;
     if (!left || !right || !depth_final || !disparity || !depth_normalized) return fail(SV_EINVAL, "null buffers");
-    if (channels != 1 && channels != 3) return fail(SV_EINVAL, "channels must be 1 or 3");
+    if (check_channels(channels)) return SV_EINVAL;
     sv::MatchPlan plan;
     rc = check_match(H, W, min_disp, num_disp, win, cost, &plan);
     if (rc) return rc;

@@ -87,7 +87,7 @@ extern "C" {
 
 int sv_refine_plan(int num_disp, int win, int* lds_bytes, int* lds_form) {
     if (num_disp <= 0 || num_disp > 512) return fail(SV_EINVAL, "num_disp must be in [1, 512]");
-    if (win < 1 || win > 15 || (win & 1) == 0) return fail(SV_EINVAL, "win must be odd in [1, 15]");
+    if (check_win(win)) return SV_EINVAL;
     if (lds_bytes) *lds_bytes = (int)sv::refine_lds_bytes(num_disp, win);
     if (lds_form) *lds_form = sv::refine_lds_form(num_disp, win) ? 1 : 0;
     return 0;

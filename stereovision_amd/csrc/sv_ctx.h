@@ -1,7 +1,8 @@
 // sv_ctx.h — the context (struct sv_ctx) and the helpers shared by the C-ABI translation
-// units: sv_capi.cpp (errors, contexts, buffers, profiling, the shared enqueue helpers),
-// sv_capi_dev.cpp (single-device entry points) and sv_capi_multi.cpp (multi-device entry
-// points).  Internal: nothing here is part of include/stereovision_amd.h.
+// units: sv_capi.cpp (errors, contexts, buffers, profiling, the shared enqueue, staging and
+// validation helpers), the single-device entry points by family (sv_capi_dev.cpp: stereo on
+// device memory; _host: stereo on host buffers; _rectify; _reduce; _fuse: fusion and its optical
+// flow; _refine) and sv_capi_multi.cpp.  Internal: not part of include/stereovision_amd.h.
 #pragma once
 #include <cstdio>
 #include <cstdlib>
@@ -16,6 +17,7 @@
 #include <vector>
 
 #include "sv_internal.h"
+#include "sv_pack.h"
 #include "sv_pool.h"
 #include "../../include/stereovision_amd.h"
 
@@ -292,6 +294,9 @@ struct SgbmParams {
 SgbmParams sgbm_reference_params(int win);
 
 int check_image(const void* a, int H, int W);
+int check_channels(int channels);   // 1 or 3
+int check_win(int win);             // odd in [1, 15]
+int check_frame_stride(int n_frames, int64_t frame_stride, int64_t frame);   // n_frames > 1: stride >= frame
 int check_match(int H, int W, int min_disp, int num_disp, int win, int cost, sv::MatchPlan* plan);
 // cv2.filterSpeckles on an int16 device map (speckle stage of SGBM, sv_filter_speckles).
 // nf > 1: a batch of maps, map z at d_img + z*fimg (one launch per stage over grid.z).
@@ -333,6 +338,10 @@ struct MapOut {
 int check_map(int fmt, const void* map, int cost, int num_disp);
 sv::PostParams map_post(int fmt, void* dst, int d8_base);
 
+// One host image (H rows of row_bytes, any stride), packed at hin + hin_off, then one H2D copy into
+// `dst` (grown here).  It never grows hin: HostBuf::ensure frees the old block, which an earlier staging
+// of the same call may still be copying from.  The caller sizes hin once, for all it stages, before that.
+int stage_image(sv_ctx* c, const void* src, int H, size_t row_bytes, size_t stride, size_t hin_off, DevBuf& dst);
 // Stage two host images (HxW or HxWx3, any stride) into the context's device gray buffers.
 int stage_pair(sv_ctx* c, const uint8_t* left, const uint8_t* right, int H, int W, int channels, int stride);
 
@@ -343,11 +352,6 @@ struct Out {
 };
 // Copy device results to caller buffers through the pinned output staging, then wait.
 int collect(sv_ctx* c, const Out* outs, int n);
-
-int make_undistort(const double* K, const double* dist, int ndist, const double* R, const double* P,
-                   int p_cols, int H, int W, sv::UndistortParams* out);
-int check_remap(const void* src, int sH, int sW, int channels, int pitch, const void* map1, int H, int W,
-                const void* dst);
 
 }  // namespace svc
 using namespace svc;
