@@ -113,7 +113,12 @@ enum sv_kernel {
     SV_K_FLOW = 19,     /* Farneback optical flow and the flow depth (every launch of sv_flow.hip) */
     SV_K_FLIP = 20,     /* k_flip_rows: the column mirrors around the right-referenced match */
     SV_K_REFINE = 21,   /* k_refine: L-R check, curvature test and sub-pixel step of a WTA map */
-    SV_NKERNELS = 22
+    SV_K_REPROJECT = 22,    /* k_reproject: the dense H x W x 3 map of a disparity map */
+    SV_K_CLOUD_MIN = 23,    /* k_cloud_min: the map's minimum (handle_missing) */
+    SV_K_CLOUD_COUNT = 24,  /* k_cloud_count: the points of every compaction tile */
+    SV_K_CLOUD_SCAN = 25,   /* k_cloud_scan: the tiles' offsets and the cloud's size */
+    SV_K_CLOUD_EMIT = 26,   /* k_cloud_emit: xyz, colours and pixel indices in pixel order */
+    SV_NKERNELS = 27
 };
 
 int sv_version(void);
@@ -535,6 +540,50 @@ int sv_disparity_refined_dev(sv_ctx* ctx, const uint8_t* d_left, const uint8_t* 
 int sv_disparity_refined(sv_ctx* ctx, const uint8_t* left, const uint8_t* right, int H, int W,
                          int channels, int stride, int min_disp, int num_disp, int win, int cost,
                          const sv_refine_params* params, int16_t* disp16);
+
+/* ---- 3D reprojection and the ordered point cloud -----------------------
+ * cv2.reprojectImageTo3D(disparity, Q, handleMissingValues, CV_32F) of a device map, and the
+ * compaction of its valid pixels into a list that keeps the pixels' row-major order.
+ * Semantics: tests/sv_cloud_oracle.py.  The map is int16 x16 (SV_DISP_I16X16: d = f32(m) / 16,
+ * the disparity create_depth_map returns) or f32 (SV_DISP_F32), row pitch `pitch` in elements;
+ * Q is any finite 4 x 4, row-major f64.
+ *
+ * sv_reproject_3d_dev: per pixel h = Q (x, y, d, 1) in f64, summed from 0 in that order;
+ * (X, Y, Z) = f32(f64(f32(h_r)) * (1 / h_3)) into d_xyz (H x W x 3, dense).  handle_missing:
+ * where |d - min(d)| <= FLT_EPSILON (the minimum ignores NaNs and the pitch padding), Z = 10000.
+ *
+ * sv_point_cloud_dev: the pixels, in row-major order, with d >= min_valid (a NaN fails), X, Y,
+ * Z finite, z_min <= Z <= z_max, inside the region of interest and, with handle_missing, not
+ * at the map's minimum.  Point k: d_xyz[3k..], d_out_bgr[3k..] = the pixel of d_bgr (H x W x 3,
+ * row pitch bgr_pitch bytes), d_index[k] = y W + x.  The outputs hold `cap` points: the first
+ * cap are written, nothing past them, and the count N is the whole cloud's.  n_points != NULL:
+ * the call waits and returns N there; NULL: nothing waits, N is in d_count once the stream has
+ * reached it.  The order is fixed by three launches (count, scan, emit), never by scheduling.
+ *
+ * SV_EINVAL before any launch: a null required pointer (the map, Q, d_xyz, the parameters),
+ * an unknown fmt, pitch < W, bgr_pitch < 3 W, H or W < 1, H W >= 2^31, cap < 0, a region that
+ * is not inside the map, a NaN in min_valid, z_min or z_max, z_min > z_max, a non-finite entry
+ * of Q, d_out_bgr without d_bgr.
+ *
+ * sv_reproject_3d / sv_point_cloud: the same on host arrays (`stride` in elements, bgr_stride
+ * in bytes); the cloud's outputs hold cap points and min(N, cap) of them are written. */
+enum { SV_DISP_I16X16 = 0, SV_DISP_F32 = 1 };
+typedef struct sv_cloud_params {
+    float min_valid, z_min, z_max;
+    int roi_x, roi_y, roi_w, roi_h;   /* roi_w or roi_h == 0: the whole map */
+    int handle_missing;
+} sv_cloud_params;
+int sv_reproject_3d_dev(sv_ctx* ctx, const void* d_disp, int fmt, int H, int W, int pitch, const double Q[16],
+                        int handle_missing, float* d_xyz, void* stream);
+int sv_point_cloud_dev(sv_ctx* ctx, const void* d_disp, int fmt, int H, int W, int pitch, const double Q[16],
+                       const uint8_t* d_bgr, int bgr_pitch, const sv_cloud_params* params, int64_t cap,
+                       float* d_xyz, uint8_t* d_out_bgr, uint32_t* d_index, uint32_t* d_count,
+                       int64_t* n_points, void* stream);
+int sv_reproject_3d(sv_ctx* ctx, const void* disp, int fmt, int H, int W, int stride, const double Q[16],
+                    int handle_missing, float* xyz);
+int sv_point_cloud(sv_ctx* ctx, const void* disp, int fmt, int H, int W, int stride, const double Q[16],
+                   const uint8_t* bgr, int bgr_stride, const sv_cloud_params* params, int64_t cap, float* xyz,
+                   uint8_t* out_bgr, uint32_t* index, int64_t* n_points);
 
 /* ---- reductions around the path ----------------------------
  * Image statistics of detect_camera_occlusion (fused_depth_map.py:131-301) for one image

@@ -532,7 +532,8 @@ void sv_destroy(sv_ctx* c) {
                           &c->sg_hsum, &c->sg_c, &c->sg_l, &c->sg_lt, &c->sg_band, &c->cc_parent,
                           &c->hist_copies, &c->cmap, &c->bgr, &c->m16,
                           &c->cc_size, &c->sg_rec, &c->gm16, &c->keys, &c->lutw, &c->fuse, &c->flow,
-                          &c->rf_img[0], &c->rf_img[1], &c->rf_map, &c->rf_right};
+                          &c->rf_img[0], &c->rf_img[1], &c->rf_map, &c->rf_right, &c->cloud, &c->cl_in[0],
+                          &c->cl_in[1], &c->cl_out[0], &c->cl_out[1], &c->cl_out[2]};
         if (c->lut_ev) (void)hipEventDestroy(c->lut_ev);
         if (c->lutw_ev) (void)hipEventDestroy(c->lutw_ev);
         if (c->scr_ev) (void)hipEventDestroy(c->scr_ev);
@@ -588,7 +589,8 @@ int sv_release_scratch(sv_ctx* c) {
     DevBuf* bufs[] = {&c->img[0], &c->img[1], &c->gray[0], &c->gray[1], &c->d16, &c->fa, &c->fb, &c->fc,
                       &c->u8, &c->harris, &c->hog[0], &c->hog[1], &c->fin, &c->sg_hsum, &c->sg_c,
                       &c->sg_l, &c->sg_lt, &c->sg_band, &c->sg_rec, &c->cc_parent, &c->cc_size, &c->m16,
-                      &c->gm16, &c->keys, &c->flow, &c->rf_img[0], &c->rf_img[1], &c->rf_map, &c->rf_right};
+                      &c->gm16, &c->keys, &c->flow, &c->rf_img[0], &c->rf_img[1], &c->rf_map, &c->rf_right,
+                      &c->cloud, &c->cl_in[0], &c->cl_in[1], &c->cl_out[0], &c->cl_out[1], &c->cl_out[2]};
     for (auto* b : bufs) b->release();
     c->d16_margins.valid = false;   // (d16's generation has changed as well)
     return 0;

@@ -2,7 +2,8 @@
 // units: sv_capi.cpp (errors, contexts, buffers, profiling, the shared enqueue, staging and
 // validation helpers), the single-device entry points by family (sv_capi_dev.cpp: stereo on
 // device memory; _host: stereo on host buffers; _rectify; _reduce; _fuse: fusion and its optical
-// flow; _refine) and sv_capi_multi.cpp.  Internal: not part of include/stereovision_amd.h.
+// flow; _refine; _cloud: 3D reprojection and the point cloud) and sv_capi_multi.cpp.  Internal: not
+// part of include/stereovision_amd.h.
 #pragma once
 #include <cstdio>
 #include <cstdlib>
@@ -122,6 +123,9 @@ struct sv_ctx {
     DevBuf flow;   // sv_flow.hip: the pyramid images, R0, R1, M and two levels' flow of sv_farneback_flow_dev
     // sv_refine.hip: the mirrored gray pair, the mirrored match and the right-referenced map
     DevBuf rf_img[2], rf_map, rf_right;
+    // sv_cloud.hip: the minimum's word, the count word and the tile counts; the host-buffer
+    // forms' staged inputs (disparity, colours) and outputs (xyz, colours, indices)
+    DevBuf cloud, cl_in[2], cl_out[3];
     uint8_t cmap_host[768] = {};   // BGR table currently in `cmap`
     bool cmap_valid = false;
     // host-buffer frame path: int16 medians come back over PCIe and are expanded on the

@@ -416,6 +416,37 @@ int launch_flip_u8(const uint8_t* s0, const uint8_t* s1, uint8_t* d0, uint8_t* d
                    int dpitch, hipStream_t s);
 int launch_flip_i16(const int16_t* src, int16_t* dst, int H, int W, int spitch, int dpitch, hipStream_t s);
 
+// 3D reprojection and the ordered point cloud (sv_cloud.hip).
+enum CloudFmt { CLOUD_I16X16 = 0, CLOUD_F32 = 1 };
+struct CloudQ {
+    double m[16];              // Q, row-major
+};
+constexpr int kCloudTile = 1024;               // pixels per compaction tile (one 256-thread block)
+constexpr uint32_t kCloudNoMin = 0xffffffffu;  // the minimum's word before any value has reached it
+struct CloudArgs {
+    const void* disp;          // int16 x16 or f32, row pitch `pitch` elements
+    int fmt, H, W, pitch;
+    CloudQ Q;
+    const uint32_t* dmin;      // the key k_cloud_min left; nullptr: no handleMissingValues
+    float* xyz;                // k_reproject: H x W x 3; the cloud: cap x 3
+    // the cloud only
+    const uint8_t* bgr;        // H x W x 3, row pitch bgr_pitch bytes (read when out_bgr is set)
+    int bgr_pitch;
+    float min_valid, z_min, z_max;
+    int rx, ry, rw, rh;        // region of interest, inside the map
+    long long cap;             // points the outputs hold
+    uint8_t* out_bgr;          // nullable
+    uint32_t* out_index;       // nullable
+    uint32_t* counts;          // cloud_tiles words: the tiles' counts, then (k_cloud_scan) their offsets
+};
+uint32_t cloud_tiles(int H, int W);
+int launch_reproject(const CloudArgs& a, hipStream_t s);
+// min over the map into *out, which holds kCloudNoMin on entry
+int launch_cloud_min(const void* disp, int fmt, int H, int W, int pitch, uint32_t* out, hipStream_t s);
+int launch_cloud_count(const CloudArgs& a, hipStream_t s);
+int launch_cloud_scan(uint32_t* counts, uint32_t nb, uint32_t* total, uint32_t* d_count, hipStream_t s);
+int launch_cloud_emit(const CloudArgs& a, hipStream_t s);
+
 // Post-processing modes for the median kernel.
 enum PostMode { POST_NONE = 0, POST_DEPTH = 1, POST_SCALED = 2 };
 struct PostParams {

@@ -26,7 +26,9 @@ POST_NONE, POST_DEPTH, POST_SCALED = 0, 1, 2
 KERNELS = {"gray": 0, "harris": 1, "hog": 2, "match": 3, "median": 4, "post": 5, "remap": 6,
            "undistort": 7, "resize": 8, "stats": 9, "select": 10, "affine": 11, "sgbm": 12,
            "speckle": 13, "gather": 14, "scatter": 15, "h2d": 16, "d2h": 17, "fuse": 18,
-           "flow": 19, "flip": 20, "refine": 21}
+           "flow": 19, "flip": 20, "refine": 21, "reproject": 22, "cloud_min": 23, "cloud_count": 24,
+           "cloud_scan": 25, "cloud_emit": 26}
+DISP_FORMATS = {"i16x16": 0, "f32": 1}   # SV_DISP_*
 
 # Every symbol include/stereovision_amd.h declares (checked by tests/test_capi.py).
 EXPORTED = [
@@ -51,7 +53,8 @@ EXPORTED = [
     "sv_fuse_blend_dev", "sv_farneback_flow_dev", "sv_fb_polyexp_dev", "sv_fb_update_matrices_dev",
     "sv_fb_blur_solve_dev", "sv_flow_depth_dev", "sv_flow_grid_dev", "sv_copy_counters",
     "sv_refine_plan", "sv_disparity_right_dev", "sv_refine_dev", "sv_disparity_refined_dev",
-    "sv_disparity_refined", "sv_ssd_mfma_query",
+    "sv_disparity_refined", "sv_ssd_mfma_query", "sv_reproject_3d_dev", "sv_point_cloud_dev",
+    "sv_reproject_3d", "sv_point_cloud",
 ]
 BAND_MARGIN = 8   # SV_BAND_MARGIN: spare rows around a band-only input buffer
 COMM_ID_BYTES = 128
@@ -201,6 +204,36 @@ def _refine_params(params) -> "_RefineParams":
     return params.c_struct()
 
 
+class _CloudParams(ctypes.Structure):
+    """sv_cloud_params."""
+    _fields_ = [("min_valid", _c_float), ("z_min", _c_float), ("z_max", _c_float), ("roi_x", _c_int),
+                ("roi_y", _c_int), ("roi_w", _c_int), ("roi_h", _c_int), ("handle_missing", _c_int)]
+
+
+def cloud_params(min_valid=0.0, z_range=None, roi=None, handle_missing=False) -> "_CloudParams":
+    """An sv_cloud_params: z_range None is (-inf, +inf), roi None the whole map."""
+    z0, z1 = (-np.inf, np.inf) if z_range is None else z_range
+    x, y, w, h = (0, 0, 0, 0) if roi is None else (int(v) for v in roi)
+    if roi is not None and (w <= 0 or h <= 0):
+        raise ValueError(f"roi {tuple(roi)}: a positive width and height expected")
+    return _CloudParams(np.float32(min_valid), np.float32(z0), np.float32(z1), x, y, w, h, 1 if handle_missing else 0)
+
+
+def _disp_format(fmt) -> int:
+    if isinstance(fmt, str):
+        if fmt not in DISP_FORMATS:
+            raise ValueError(f"unknown disparity format {fmt!r}; expected one of {sorted(DISP_FORMATS)}")
+        return DISP_FORMATS[fmt]
+    return int(fmt)
+
+
+def _q16(Q) -> np.ndarray:
+    q = np.ascontiguousarray(Q, np.float64)
+    if q.shape != (4, 4):
+        raise ValueError(f"Q: a 4 x 4 matrix expected, got shape {q.shape}")
+    return q
+
+
 def map_out(mode: int = POST_NONE, disparity: int = 0, out_a: int = 0, out_u8: int = 0, out_b: int = 0,
             med16: int = 0, d8: int = 0, harris: int = 0, bgr: int = 0, cmap=None, min_depth=0.0,
             max_depth=0.0, min_disp_global=0.0) -> MapOut:
@@ -325,6 +358,14 @@ def _declare(lib):
                                                                       _c_int, _vp], _c_int),
         "sv_disparity_refined": ([_vp, _u8p, _u8p] + [_c_int] * 8 + [ctypes.POINTER(_RefineParams), _i16p],
                                  _c_int),
+        "sv_reproject_3d_dev": ([_vp, _vp, _c_int, _c_int, _c_int, _c_int, _f64p, _c_int, _vp, _vp], _c_int),
+        "sv_point_cloud_dev": ([_vp, _vp, _c_int, _c_int, _c_int, _c_int, _f64p, _vp, _c_int,
+                                ctypes.POINTER(_CloudParams), ctypes.c_int64, _vp, _vp, _vp, _vp,
+                                ctypes.POINTER(ctypes.c_int64), _vp], _c_int),
+        "sv_reproject_3d": ([_vp, _vp, _c_int, _c_int, _c_int, _c_int, _f64p, _c_int, _f32p], _c_int),
+        "sv_point_cloud": ([_vp, _vp, _c_int, _c_int, _c_int, _c_int, _f64p, _NullableU8, _c_int,
+                            ctypes.POINTER(_CloudParams), ctypes.c_int64, _f32p, _NullableU8, _vp,
+                            ctypes.POINTER(ctypes.c_int64)], _c_int),
         "sv_sgbm": ([_vp, _u8p, _u8p] + [_c_int] * 14 + [_i16p], _c_int),
         "sv_sgbm_dev": ([_vp, _vp, _vp] + [_c_int] * 13 + [_vp, _c_int, _vp], _c_int),
         "sv_filter_speckles": ([_vp, _i16p] + [_c_int] * 5, _c_int),
@@ -813,6 +854,57 @@ class Engine:
                     self.to_host(d_u8, (H, W), np.uint8),
                     self.to_host(d_b, (H, W), np.float32) if scaled else None,
                     self.to_host(d_bgr, (H, W, 3), np.uint8) if d_bgr else None)
+
+    # -- 3D reprojection and the ordered point cloud -----------------------------
+    def reproject_3d_dev(self, d_disp: int, fmt, H: int, W: int, pitch: int, Q, handle_missing: bool,
+                         d_xyz: int, stream: int = 0):
+        """sv_reproject_3d_dev: the dense H x W x 3 float32 map of a device disparity map
+        (fmt "i16x16" or "f32", pitch in elements)."""
+        _check("sv_reproject_3d_dev", self.lib.sv_reproject_3d_dev(
+            self._h, d_disp, _disp_format(fmt), H, W, pitch, _q16(Q), 1 if handle_missing else 0, d_xyz,
+            stream or None))
+
+    def reproject_3d(self, disparity: np.ndarray, Q, handle_missing: bool = False) -> np.ndarray:
+        """cv2.reprojectImageTo3D of a host int16 x16 or float32 H x W map."""
+        d = np.ascontiguousarray(disparity)
+        H, W = d.shape
+        out = np.empty((H, W, 3), np.float32)
+        _check("sv_reproject_3d", self.lib.sv_reproject_3d(
+            self._h, d.ctypes.data, DISP_FORMATS["i16x16" if d.dtype == np.int16 else "f32"], H, W, W, _q16(Q),
+            1 if handle_missing else 0, out))
+        return out
+
+    def point_cloud_dev(self, d_disp: int, fmt, H: int, W: int, pitch: int, Q, params: "_CloudParams", cap: int,
+                        d_xyz: int, d_bgr: int = 0, bgr_pitch: int = 0, d_out_bgr: int = 0, d_index: int = 0,
+                        d_count: int = 0, wait: bool = True, stream: int = 0):
+        """sv_point_cloud_dev: the valid pixels in row-major order into d_xyz (cap x 3 float32),
+        d_out_bgr (cap x 3 uint8) and d_index (cap uint32).  wait: returns the cloud's size N (one
+        4-byte read); otherwise nothing waits, None is returned and N is in d_count."""
+        n = ctypes.c_int64(0)
+        _check("sv_point_cloud_dev", self.lib.sv_point_cloud_dev(
+            self._h, d_disp, _disp_format(fmt), H, W, pitch, _q16(Q), d_bgr or None, bgr_pitch,
+            ctypes.byref(params), int(cap), d_xyz, d_out_bgr or None, d_index or None, d_count or None,
+            ctypes.byref(n) if wait else None, stream or None))
+        return int(n.value) if wait else None
+
+    def point_cloud(self, disparity: np.ndarray, Q, colors, params: "_CloudParams", cap: int | None = None,
+                    with_index: bool = False):
+        """sv_point_cloud on host arrays -> (xyz, bgr or None, index or None, N); the arrays hold
+        min(N, cap) points."""
+        d = np.ascontiguousarray(disparity)
+        H, W = d.shape
+        cap = H * W if cap is None else int(cap)
+        room = max(min(cap, H * W), 0)
+        xyz = np.empty((room, 3), np.float32)
+        bgr = np.empty((room, 3), np.uint8) if colors is not None else None
+        idx = np.empty(room, np.uint32) if with_index else None
+        n = ctypes.c_int64(0)
+        _check("sv_point_cloud", self.lib.sv_point_cloud(
+            self._h, d.ctypes.data, DISP_FORMATS["i16x16" if d.dtype == np.int16 else "f32"], H, W, W, _q16(Q),
+            None if colors is None else np.ascontiguousarray(colors), 3 * W, ctypes.byref(params), cap, xyz, bgr,
+            None if idx is None else idx.ctypes.data, ctypes.byref(n)))
+        m = min(int(n.value), room)
+        return xyz[:m], None if bgr is None else bgr[:m], None if idx is None else idx[:m], int(n.value)
 
     def disparity_rows(self, left, right, min_disp: int, num_disp: int, win: int, row0: int,
                        row1: int, cost="sad", out: np.ndarray | None = None) -> np.ndarray:

@@ -12,6 +12,7 @@ reference's order and with its decisions:
   MiDaS branch (:2719-2774)        the caller's map, calibrated to the stereo maps or min-max normalised
   flow normalisation (:2793-2811)  one elementwise pass (``k_affine_f32`` modes 3 and 4)
   fuse (:2822-2842)                ``fusion.fuse_maps_dev`` under fuse_depth_maps' validity rules
+  cloud (not in the reference)     opt-in: ``cloud.point_cloud_dev`` on the stereo disparity and the left frame
 
 UI, capture, frame skipping, the keyboard handlers and the legends are not part of it, and MiDaS
 is a map the caller supplies: the process stays torch-free.  Everything is enqueued on the
@@ -19,10 +20,12 @@ engine's context stream.  What still crosses to the host per frame is listed in 
 """
 from __future__ import annotations
 
+import dataclasses
 import traceback
 
 import numpy as np
 
+from . import cloud as _cloud
 from . import colormap
 from . import flow as _flow
 from . import fusion as _fusion
@@ -80,7 +83,9 @@ class OcclusionSwitch:
 
 class FrameResult:
     """One step's scalars, the host arrays of the requested outputs (attributes named as in
-    OUTPUT_NAMES; None when the map does not exist this frame) and the device maps."""
+    OUTPUT_NAMES; None when the map does not exist this frame) and the device maps.  ``cloud``:
+    the frame's point cloud, (xyz, bgr[, index]) as cloud.point_cloud returns it, for a pipeline
+    built with ``cloud=``; None when stereo did not run this frame or the calibration has no Q."""
 
     def __init__(self):
         self.occlusion_state = "none"
@@ -91,6 +96,7 @@ class FrameResult:
         self.mode_text = None
         self.range = None
         self.source = "left"
+        self.cloud = None
         self._dev = {}
         for name in OUTPUT_NAMES:
             setattr(self, name, None)
@@ -105,6 +111,13 @@ class FrameResult:
         return self._dev.get(name)
 
 
+def calib_q(calib):
+    """The calibration's disparity-to-3D matrix, or None when it has none."""
+    if calib is None or "Q" not in calib or calib["Q"] is None:
+        return None
+    return calib["Q"]
+
+
 def _log(stage: str, e: Exception) -> None:
     print(f"[{stage} error] {e}")
     traceback.print_exc()
@@ -116,7 +129,7 @@ class FusionFramePipeline:
     def __init__(self, stereo_calib=None, *, use_rectify=True, min_disp=None, num_disp=None,
                  window_size=None, cost=None, engine=None, outputs=("fused_u8", "fused_colormap"),
                  occlusion_check_interval=2, occlusion_hysteresis_frames=5, occlusion_threshold=0.45,
-                 min_inliers=15, motion_timeout=1.5, refine=None):
+                 min_inliers=15, motion_timeout=1.5, refine=None, cloud=None):
         outputs = tuple(outputs)
         unknown = [n for n in outputs if n not in OUTPUT_NAMES]
         if unknown:
@@ -127,6 +140,11 @@ class FusionFramePipeline:
         self.use_rectify = bool(use_rectify)
         self.min_disp, self.num_disp, self.window_size, self.cost = min_disp, num_disp, window_size, cost
         self.refine = refine        # engine.RefineParams; None: fused_depth_map.REFINE at each step
+        if cloud is not None:
+            if not isinstance(cloud, _cloud.CloudParams):
+                raise TypeError(f"cloud: CloudParams expected, got {type(cloud).__name__}")
+            cloud.check()
+        self.cloud = cloud          # cloud.CloudParams; None: no point cloud (min_disp: the stereo step's)
         self.outputs = outputs
         self.occlusion_threshold = occlusion_threshold
         self.use_midas = True
@@ -486,6 +504,18 @@ class FusionFramePipeline:
                     info = None
                     dev.pop("fused_u8", None)
                     dev.pop("fused_colormap", None)
+
+        if self.cloud is not None and stereo_ok and calib_q(self.stereo_calib) is not None:   # 9
+            try:
+                res.cloud = _cloud.point_cloud_dev(
+                    eng, stereo["stereo_disparity"], "f32", H, W, calib_q(self.stereo_calib), d_l,
+                    dataclasses.replace(self.cloud, min_disp=settings[0]),
+                    bufs=lambda name, nbytes: self._buf("cloud_" + name, nbytes))
+            except EngineUnavailable:
+                raise
+            except Exception as e:
+                _log("Point cloud", e)
+                res.cloud = None
 
         # the scalars, then the requested maps
         res.occlusion_state, res.left_score, res.right_score = sw.state, self.left_score, self.right_score
