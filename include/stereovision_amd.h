@@ -83,8 +83,11 @@ typedef struct sv_ctx sv_ctx;
  * algorithm restated (the reference's own matcher), with the reference's parameters
  * P1 = 24 win^2, P2 = 96 win^2, disp12MaxDiff 1, uniquenessRatio 10, speckle 100 / 32,
  * preFilterCap 63 (depth_map.py:894-906) when selected through the generic entry points;
- * sv_sgbm / sv_sgbm_dev take every parameter.  SGBM is frame-only (no row bands). */
-enum sv_cost { SV_COST_SAD = 0, SV_COST_SSD = 1, SV_COST_HOG = 2, SV_COST_SGBM = 3 };
+ * sv_sgbm / sv_sgbm_dev take every parameter.  SGBM is frame-only (no row bands).
+ * CENSUS: winner-take-all over the Hamming distance of 9 x 7 census codes (sv_census_dev
+ * below): unchanged by any monotone brightness change of either frame.  win odd in [1, 15],
+ * num_disp in [1, 512]; the map is the int16 x16 whole-pixel map of SAD / SSD / HOG. */
+enum sv_cost { SV_COST_SAD = 0, SV_COST_SSD = 1, SV_COST_HOG = 2, SV_COST_SGBM = 3, SV_COST_CENSUS = 4 };
 
 enum sv_status {
     SV_OK = 0,
@@ -118,7 +121,8 @@ enum sv_kernel {
     SV_K_CLOUD_COUNT = 24,  /* k_cloud_count: the points of every compaction tile */
     SV_K_CLOUD_SCAN = 25,   /* k_cloud_scan: the tiles' offsets and the cloud's size */
     SV_K_CLOUD_EMIT = 26,   /* k_cloud_emit: xyz, colours and pixel indices in pixel order */
-    SV_NKERNELS = 27
+    SV_K_CENSUS = 27,       /* k_census: the census transform (k_census_match counts as SV_K_MATCH) */
+    SV_NKERNELS = 28
 };
 
 int sv_version(void);
@@ -540,6 +544,35 @@ int sv_disparity_refined_dev(sv_ctx* ctx, const uint8_t* d_left, const uint8_t* 
 int sv_disparity_refined(sv_ctx* ctx, const uint8_t* left, const uint8_t* right, int H, int W,
                          int channels, int stride, int min_disp, int num_disp, int win, int cost,
                          const sv_refine_params* params, int16_t* disp16);
+
+/* ---- census / Hamming cost ----------------------------------------------
+ * Semantics: tests/sv_census_oracle.py.  Every entry point that takes a `cost` accepts
+ * SV_COST_CENSUS and runs the two steps below on the context's scratch; in the refinement stage
+ * census maps take the left-right check and the speckle filter only (subpixel or
+ * min_curvature > 0: SV_EINVAL).
+ *
+ * sv_census_dev: the census code C(x, y) of rows [row0, row1) (clamped to [0, H)) of a gray
+ * image, one little-endian uint64 per pixel, row pitch code_pitch in elements; other rows and
+ * the pitch padding are left untouched.  The 9-wide x 7-tall neighbourhood is enumerated
+ * row-major, dy = -3..3 outer, dx = -4..4 inner, skipping (0, 0): k = 0..61.  Bit k is 1 iff
+ * Ip(x + dx, y + dy) < I(x, y) (strict), Ip the replicate-clamped image; bits 62 and 63 are 0.
+ * Image rows [row0 - 3, row1 + 3) of [0, H) are read.
+ *
+ * sv_census_match_dev: winner-take-all over two code planes (the transform's, or any caller's
+ * 64-bit binary descriptors): cost(x, y, d) = sum over |i|, |j| <= win / 2 of
+ * popcount(CLp(x + i, y + j) xor CRp(x + i - d, y + j)), CLp / CRp the planes with
+ * replicate-clamped coordinates, all 64 bits counted; d* = the first argmin over d in [min_disp,
+ * min_disp + num_disp).  Every element of rows [row0, row1) of d_disp16 (width W, pitch
+ * out_pitch elements) is written: d* x 16 inside the matched column band [max(min_disp +
+ * num_disp, 0), W + min(min_disp, 0)), (min_disp - 1) x 16 outside it.  Code rows [row0 - win / 2,
+ * row1 + win / 2) of [0, H) are read.  A cost is at most 64 * 15^2 = 14400, so no SV_ERANGE
+ * case exists.  SV_EINVAL before any launch: null pointers, a pitch < W, an even win or one
+ * outside [1, 15], num_disp outside [1, 512], the int16 range rule. */
+int sv_census_dev(sv_ctx* ctx, const uint8_t* d_gray, int H, int W, int pitch, int row0, int row1,
+                  uint64_t* d_codes, int code_pitch, void* stream);
+int sv_census_match_dev(sv_ctx* ctx, const uint64_t* d_codes_left, const uint64_t* d_codes_right,
+                        int H, int W, int code_pitch, int min_disp, int num_disp, int win,
+                        int row0, int row1, int16_t* d_disp16, int out_pitch, void* stream);
 
 /* ---- 3D reprojection and the ordered point cloud -----------------------
  * cv2.reprojectImageTo3D(disparity, Q, handleMissingValues, CV_32F) of a device map, and the

@@ -2,7 +2,7 @@
 // contexts, device memory, profiling and the enqueue, staging and validation helpers every
 // entry point shares (sv_ctx.h).  The entry points themselves, one file per family: sv_capi_dev.cpp
 // (stereo on device memory), _host (stereo on host buffers), _rectify, _reduce, _fuse (fusion and its
-// optical flow), _refine, and sv_capi_multi.cpp (several devices, RCCL / peer-copy gathers).
+// optical flow), _refine, _census, and sv_capi_multi.cpp (several devices, RCCL / peer-copy gathers).
 //
 // A context = one device + one HIP stream + grow-only device buffers + pinned staging.
 // Host entry points stage into pinned memory, run the whole chain on the context stream
@@ -47,6 +47,9 @@ int check_match(int H, int W, int min_disp, int num_disp, int win, int cost, sv:
         return fail(SV_EINVAL, "disparity range beyond the int16 x16 map: min_disp >= -2047 and "
                                "min_disp + num_disp - 1 <= 2047 required");
     if (cost == SV_COST_SGBM) return 0;   // no lane plan: sv_sgbm.hip sizes itself
+    // census: a window cost is at most 64 * 15^2 = 14400 < 2^14 and the index takes 9 bits, so
+    // every key fits 23 bits (no SV_ERANGE case) and k_census_match needs no lane plan
+    if (cost == SV_COST_CENSUS) return 0;
     int rc = sv::plan_match(num_disp, win, cost, plan);
     if (rc == -34) return fail(SV_ERANGE, "cost range too large for the argmin key");
     if (rc != 0) return fail(SV_EINVAL, "unsupported (num_disp, win, cost)");
@@ -217,10 +220,41 @@ static sv::MatchParams match_geometry(const uint8_t* L, const uint8_t* R, int H,
     return a;
 }
 
+int enqueue_census_match(sv_ctx* c, const uint64_t* CL, const uint64_t* CR, int H, int W, int cpitch, int min_disp,
+                         int num_disp, int win, int row0, int row1, int16_t* out, int opitch, hipStream_t s, int nf,
+                         long long fs_codes, long long fs_out) {
+    // (the band and the batch fields as every matcher launch has them)
+    const sv::MatchParams g = match_geometry(nullptr, nullptr, H, W, 0, min_disp, num_disp, win, SV_COST_CENSUS, row0,
+                                             row1, out, opitch, nf, 0, fs_out);
+    sv::CensusMatchArgs a{};
+    a.CL = CL;
+    a.CR = CR;
+    a.H = H;
+    a.W = W;
+    a.cpitch = cpitch;
+    a.minD = min_disp;
+    a.D = num_disp;
+    a.r = g.r;
+    a.X0 = g.X0;
+    a.X1 = g.X1;
+    a.row0 = row0;
+    a.row1 = row1;
+    a.out = out;
+    a.opitch = opitch;
+    a.nf = g.nf;
+    a.fs_codes = g.nf > 1 ? fs_codes : 0;
+    a.fs_out = g.nf > 1 ? fs_out : 0;
+    c->scratch_written(out);
+    SV_LAUNCH(c, SV_K_MATCH, s, sv::launch_census_match(a, s));
+    return 0;
+}
+
 // Enqueue disparity for rows [row0,row1) of gray device images.
 // nf > 1: a batch of frames, frame z at L/R + z*fs_in bytes and out + z*fs_out elements
 // (one launch over grid.z; HOG: one histogram launch over both images of every frame, then
-// one match launch reading frame z's histograms at z * H*W*10).
+// one match launch reading frame z's histograms at z * H*W*10; census: one transform launch
+// over both images of every frame, then one match launch reading frame z's code planes at
+// z * H*W).
 int enqueue_disparity(sv_ctx* c, const uint8_t* L, const uint8_t* R, int H, int W, int pitch,
                       int min_disp, int num_disp, int win, int cost, int row0, int row1,
                       int16_t* out, int opitch, hipStream_t s, int nf, long long fs_in,
@@ -238,6 +272,29 @@ int enqueue_disparity(sv_ctx* c, const uint8_t* L, const uint8_t* R, int H, int 
         if (row0 != 0 || row1 != H) return fail(SV_EINVAL, "SGBM cannot compute a row band (use frames)");
         return enqueue_sgbm(c, L, R, H, W, pitch, min_disp, num_disp, win, sgbm_reference_params(win), out, opitch,
                             s, nf, fs_in, fs_out);
+    }
+    if (cost == SV_COST_CENSUS) {
+        const int r = win / 2, n = nf < 1 ? 1 : nf;
+        const long long fc = (long long)H * W;   // elements per frame's code plane
+        SV_HIP(c->census[0].ensure((size_t)fc * sizeof(uint64_t) * n));
+        SV_HIP(c->census[1].ensure((size_t)fc * sizeof(uint64_t) * n));
+        sv::CensusArgs t{};
+        t.g0 = L;
+        t.g1 = R;
+        t.H = H;
+        t.W = W;
+        t.pitch = pitch;
+        t.y0 = std::max(row0 - r, 0);   // the code rows the matcher reads
+        t.y1 = std::min(row1 + r, H);
+        t.c0 = c->census[0].as<uint64_t>();
+        t.c1 = c->census[1].as<uint64_t>();
+        t.cpitch = W;
+        t.nz = 2 * n;
+        t.fs_in = n > 1 ? fs_in : 0;
+        t.fs_codes = fc;
+        SV_LAUNCH(c, SV_K_CENSUS, s, sv::launch_census(t, s));
+        return enqueue_census_match(c, t.c0, t.c1, H, W, W, min_disp, num_disp, win, row0, row1, out, opitch, s, n, fc,
+                                    fs_out);
     }
     sv::MatchParams a = match_geometry(L, R, H, W, pitch, min_disp, num_disp, win, cost, row0, row1, out, opitch, nf,
                                        fs_in, fs_out);
@@ -533,7 +590,8 @@ void sv_destroy(sv_ctx* c) {
                           &c->hist_copies, &c->cmap, &c->bgr, &c->m16,
                           &c->cc_size, &c->sg_rec, &c->gm16, &c->keys, &c->lutw, &c->fuse, &c->flow,
                           &c->rf_img[0], &c->rf_img[1], &c->rf_map, &c->rf_right, &c->cloud, &c->cl_in[0],
-                          &c->cl_in[1], &c->cl_out[0], &c->cl_out[1], &c->cl_out[2]};
+                          &c->cl_in[1], &c->cl_out[0], &c->cl_out[1], &c->cl_out[2], &c->census[0],
+                          &c->census[1]};
         if (c->lut_ev) (void)hipEventDestroy(c->lut_ev);
         if (c->lutw_ev) (void)hipEventDestroy(c->lutw_ev);
         if (c->scr_ev) (void)hipEventDestroy(c->scr_ev);
@@ -590,7 +648,8 @@ int sv_release_scratch(sv_ctx* c) {
                       &c->u8, &c->harris, &c->hog[0], &c->hog[1], &c->fin, &c->sg_hsum, &c->sg_c,
                       &c->sg_l, &c->sg_lt, &c->sg_band, &c->sg_rec, &c->cc_parent, &c->cc_size, &c->m16,
                       &c->gm16, &c->keys, &c->flow, &c->rf_img[0], &c->rf_img[1], &c->rf_map, &c->rf_right,
-                      &c->cloud, &c->cl_in[0], &c->cl_in[1], &c->cl_out[0], &c->cl_out[1], &c->cl_out[2]};
+                      &c->cloud, &c->cl_in[0], &c->cl_in[1], &c->cl_out[0], &c->cl_out[1], &c->cl_out[2],
+                      &c->census[0], &c->census[1]};
     for (auto* b : bufs) b->release();
     c->d16_margins.valid = false;   // (d16's generation has changed as well)
     return 0;
@@ -626,7 +685,7 @@ int sv_ssd_mfma_query(const uint8_t* d_left, const uint8_t* d_right, int H, int 
     sv::MatchPlan plan;
     const int rc = check_match(H, W, min_disp, num_disp, win, cost, &plan);
     if (rc) return rc;
-    if (cost == SV_COST_SGBM) return 0;
+    if (cost == SV_COST_SGBM || cost == SV_COST_CENSUS) return 0;
     if (row0 < 0) row0 = 0;
     if (row1 > H) row1 = H;
     const sv::MatchParams a = match_geometry(d_left, d_right, H, W, pitch, min_disp, num_disp, win, cost, row0, row1,

@@ -11,7 +11,7 @@ int check_stage(const void* d_left, const void* d_right, int H, int W, int pitch
     if (check_image(d_left, H, W) || check_image(d_right, H, W)) return SV_EINVAL;
     if (pitch < W || out_pitch < W) return fail(SV_EINVAL, "pitch smaller than width");
     if (H > 65535) return fail(SV_EINVAL, "refinement: more than 65535 rows");
-    if (cost == SV_COST_SGBM) return fail(SV_EINVAL, "the refinement stage takes SAD, SSD and HOG maps, not SGBM");
+    if (cost == SV_COST_SGBM) return fail(SV_EINVAL, "the refinement stage takes SAD, SSD, HOG and census maps, not SGBM");
     sv::MatchPlan plan;
     return check_match(H, W, min_disp, num_disp, win, cost, &plan);
 }
@@ -21,6 +21,8 @@ int check_params(const sv_refine_params* p, int cost) {
     if (p->min_curvature < 0) return fail(SV_EINVAL, "min_curvature must be >= 0");
     if (cost == SV_COST_HOG && (p->subpixel || p->min_curvature > 0))
         return fail(SV_EINVAL, "HOG maps take the left-right check and the speckle filter only");
+    if (cost == SV_COST_CENSUS && (p->subpixel || p->min_curvature > 0))
+        return fail(SV_EINVAL, "census maps take the left-right check and the speckle filter only");
     return 0;
 }
 

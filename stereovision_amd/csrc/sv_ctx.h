@@ -2,7 +2,8 @@
 // units: sv_capi.cpp (errors, contexts, buffers, profiling, the shared enqueue, staging and
 // validation helpers), the single-device entry points by family (sv_capi_dev.cpp: stereo on
 // device memory; _host: stereo on host buffers; _rectify; _reduce; _fuse: fusion and its optical
-// flow; _refine; _cloud: 3D reprojection and the point cloud) and sv_capi_multi.cpp.  Internal: not
+// flow; _refine; _cloud: 3D reprojection and the point cloud; _census: the census / Hamming cost) and
+// sv_capi_multi.cpp.  Internal: not
 // part of include/stereovision_amd.h.
 #pragma once
 #include <cstdio>
@@ -126,6 +127,8 @@ struct sv_ctx {
     // sv_cloud.hip: the minimum's word, the count word and the tile counts; the host-buffer
     // forms' staged inputs (disparity, colours) and outputs (xyz, colours, indices)
     DevBuf cloud, cl_in[2], cl_out[3];
+    // sv_census.hip: the left and right code planes of cost = SV_COST_CENSUS (8 H W bytes per frame)
+    DevBuf census[2];
     uint8_t cmap_host[768] = {};   // BGR table currently in `cmap`
     bool cmap_valid = false;
     // host-buffer frame path: int16 medians come back over PCIe and are expanded on the
@@ -318,6 +321,12 @@ int enqueue_disparity(sv_ctx* c, const uint8_t* L, const uint8_t* R, int H, int 
                       int min_disp, int num_disp, int win, int cost, int row0, int row1,
                       int16_t* out, int opitch, hipStream_t s, int nf = 1, long long fs_in = 0,
                       long long fs_out = 0, bool track_margins = false);
+// The fused Hamming matcher over two code planes (sv_census.hip): rows [row0, row1) of nf maps,
+// frame z's planes at CL / CR + z*fs_codes elements and its map at out + z*fs_out.  Arguments
+// already validated (check_match with SV_COST_CENSUS), rows clamped to [0, H].
+int enqueue_census_match(sv_ctx* c, const uint64_t* CL, const uint64_t* CR, int H, int W, int cpitch, int min_disp,
+                         int num_disp, int win, int row0, int row1, int16_t* out, int opitch, hipStream_t s,
+                         int nf = 1, long long fs_codes = 0, long long fs_out = 0);
 // Attach the cached post-processing table (whole: the map holds whole disparities only).
 int attach_lut(sv_ctx* c, sv::PostParams& pp, hipStream_t s, bool whole = false);
 // Device copy of a 256-entry BGR colormap table (re-uploaded only when it changes).

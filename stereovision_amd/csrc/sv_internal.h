@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <algorithm>
 #include <cstdlib>
 #include <string>
 
@@ -53,7 +54,7 @@ int comm_rank(const sv_comm* c);
 int comm_size(const sv_comm* c);
 int comm_device(const sv_comm* c);
 
-enum Cost { COST_SAD = 0, COST_SSD = 1, COST_HOG = 2, COST_SGBM = 3 };
+enum Cost { COST_SAD = 0, COST_SSD = 1, COST_HOG = 2, COST_SGBM = 3, COST_CENSUS = 4 };
 
 // Disparity lanes: each wave is split into groups of LPG lanes (16/32/64); every lane of a
 // group owns DPL consecutive disparities of the same output pixel, so one group covers
@@ -135,6 +136,40 @@ int launch_hog_hist(const uint8_t* g, int H, int W, int pitch, int win, int row0
 int launch_hog_hist_pairs(const uint8_t* g0, const uint8_t* g1, int H, int W, int pitch, int win, int row0,
                           int row1, uint16_t* h0, uint16_t* h1, int nf, long long fs_in, long long fs_hist,
                           hipStream_t s);
+
+// Census / Hamming cost (sv_census.hip).  A code plane holds one little-endian
+// uint64 per pixel, row pitch `cpitch` elements: bit k = 0..61 over dy = -3..3 (outer), dx =
+// -4..4 (inner) without (0, 0) is Ip(x + dx, y + dy) < I(x, y) on the replicate-clamped image.
+struct CensusArgs {
+    const uint8_t* g0;         // gray images, row pitch `pitch` bytes
+    const uint8_t* g1;         // the pair's second image (nz > 1)
+    int H, W, pitch;
+    int y0, y1;                // code rows written, inside [0, H); image rows read: [y0 - 3, y1 + 3) clamped to [0, H)
+    uint64_t* c0;
+    uint64_t* c1;
+    int cpitch;
+    // images per launch (grid.z): 1 (g0 -> c0), or 2 nf: z = 2 * frame + side, frame f's images
+    // at g0 / g1 + f * fs_in bytes and its planes at c0 / c1 + f * fs_codes elements
+    int nz;
+    long long fs_in, fs_codes;
+};
+// cost(x, y, d) = sum over the win x win window of popcount(CLp(x+i, y+j) ^ CRp(x+i-d, y+j)), the
+// planes' coordinates replicate-clamped, all 64 bits counted; first argmin over the sweep.  Fields
+// as in MatchParams: every element of rows [row0, row1) of width W is written, (minD + idx) * 16
+// inside [X0, X1) and (minD - 1) * 16 outside; code rows [row0 - r, row1 + r) of [0, H) are read.
+struct CensusMatchArgs {
+    const uint64_t* CL;
+    const uint64_t* CR;
+    int H, W, cpitch;
+    int minD, D, r;
+    int X0, X1, row0, row1;
+    int16_t* out;
+    int opitch;
+    int nf;                    // grid.z: frame z's planes at + z * fs_codes, its map at + z * fs_out
+    long long fs_codes, fs_out;
+};
+int launch_census(const CensusArgs& a, hipStream_t s);
+int launch_census_match(const CensusMatchArgs& a, hipStream_t s);
 
 // Rectification (sv_rectify.hip).  ir = inv(P[:, :3] * R) row-major; k = k1 k2 p1 p2 k3 k4
 // k5 k6 s1 s2 s3 s4 (OpenCV distCoeffs order, zero-padded).

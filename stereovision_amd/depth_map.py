@@ -33,7 +33,9 @@ STEREO_CALIBRATION_FILE = "output/stereo_calibration_data.pkl"   # depth_map.py:
 MIN_DISP = 16 * 0
 NUM_DISP = 16 * 20
 WINDOW_SIZE = 7
-# Cost function of the north_star engine that replaces StereoSGBM: "sad" | "ssd" | "hog".
+# Cost function of the north_star engine that replaces StereoSGBM: "sad" | "ssd" | "hog" |
+# "census" (Hamming distance of 9 x 7 census codes: unchanged by exposure differences between
+# the two cameras).
 COST = "sad"
 # engine.RefineParams: run the refinement stage (left-right check, curvature test, sub-pixel step,
 # speckle filter) between the match and the median.  None: the plain path.

@@ -21,13 +21,13 @@ import numpy as np
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SV_LIB_PATH", os.path.join(_HERE, "lib", "libsvhip.so"))
 
-COSTS = {"sad": 0, "ssd": 1, "hog": 2, "sgbm": 3}
+COSTS = {"sad": 0, "ssd": 1, "hog": 2, "sgbm": 3, "census": 4}
 POST_NONE, POST_DEPTH, POST_SCALED = 0, 1, 2
 KERNELS = {"gray": 0, "harris": 1, "hog": 2, "match": 3, "median": 4, "post": 5, "remap": 6,
            "undistort": 7, "resize": 8, "stats": 9, "select": 10, "affine": 11, "sgbm": 12,
            "speckle": 13, "gather": 14, "scatter": 15, "h2d": 16, "d2h": 17, "fuse": 18,
            "flow": 19, "flip": 20, "refine": 21, "reproject": 22, "cloud_min": 23, "cloud_count": 24,
-           "cloud_scan": 25, "cloud_emit": 26}
+           "cloud_scan": 25, "cloud_emit": 26, "census": 27}
 DISP_FORMATS = {"i16x16": 0, "f32": 1}   # SV_DISP_*
 
 # Every symbol include/stereovision_amd.h declares (checked by tests/test_capi.py).
@@ -54,7 +54,7 @@ EXPORTED = [
     "sv_fb_blur_solve_dev", "sv_flow_depth_dev", "sv_flow_grid_dev", "sv_copy_counters",
     "sv_refine_plan", "sv_disparity_right_dev", "sv_refine_dev", "sv_disparity_refined_dev",
     "sv_disparity_refined", "sv_ssd_mfma_query", "sv_reproject_3d_dev", "sv_point_cloud_dev",
-    "sv_reproject_3d", "sv_point_cloud",
+    "sv_reproject_3d", "sv_point_cloud", "sv_census_dev", "sv_census_match_dev",
 ]
 BAND_MARGIN = 8   # SV_BAND_MARGIN: spare rows around a band-only input buffer
 COMM_ID_BYTES = 128
@@ -176,7 +176,7 @@ class _RefineParams(ctypes.Structure):
 class RefineParams:
     """Settings of the refinement stage of a SAD / SSD / HOG map (sv_refine_params):
     lr_max_diff < 0 switches the left-right check off, min_curvature 0 the curvature test,
-    speckle_window 0 the speckle filter.  HOG maps take the check and the filter only."""
+    speckle_window 0 the speckle filter.  HOG and census maps take the check and the filter only."""
 
     def __init__(self, lr_max_diff: int = 1, min_curvature: int = 1, subpixel: bool = True,
                  speckle_window: int = 0, speckle_range: int = 2):
@@ -295,6 +295,8 @@ def _declare(lib):
         "sv_harris_dev": ([_vp, _vp, _c_int, _c_int, _c_int, _vp, _vp], _c_int),
         "sv_hog_hist_dev": ([_vp, _vp, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _vp, _vp],
                             _c_int),
+        "sv_census_dev": ([_vp, _vp, _c_int, _c_int, _c_int, _c_int, _c_int, _vp, _c_int, _vp], _c_int),
+        "sv_census_match_dev": ([_vp, _vp, _vp] + [_c_int] * 8 + [_vp, _c_int, _vp], _c_int),
         "sv_disparity_rows": ([_vp, _u8p, _u8p, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int,
                                _c_int, _c_int, _c_int, _c_int, _i16p], _c_int),
         "sv_dev_alloc": ([_vp, ctypes.c_uint64, ctypes.POINTER(_vp)], _c_int),
@@ -1221,6 +1223,58 @@ class Engine:
                      row1: int, d_out: int, stream: int = 0):
         _check("sv_hog_hist_dev", self.lib.sv_hog_hist_dev(self._h, d_gray, H, W, pitch, win,
                                                            row0, row1, d_out, stream or None))
+
+    # -- census / Hamming cost ------------------------------------------------------------
+    def census_dev(self, d_gray: int, H: int, W: int, pitch: int, row0: int, row1: int, d_codes: int,
+                   code_pitch: int, stream: int = 0):
+        """sv_census_dev: the 9 x 7 census codes (uint64, row pitch `code_pitch` elements) of
+        rows [row0, row1) of a gray device image."""
+        _check("sv_census_dev", self.lib.sv_census_dev(self._h, d_gray, int(H), int(W), int(pitch), int(row0),
+                                                       int(row1), d_codes, int(code_pitch), stream or None))
+
+    def census_match_dev(self, d_codes_left: int, d_codes_right: int, H: int, W: int, code_pitch: int,
+                         min_disp: int, num_disp: int, win: int, row0: int, row1: int, d_disp16: int,
+                         out_pitch: int, stream: int = 0):
+        """sv_census_match_dev: winner-take-all Hamming matching of two uint64 code planes into
+        rows [row0, row1) of an int16 x16 device map."""
+        _check("sv_census_match_dev", self.lib.sv_census_match_dev(
+            self._h, d_codes_left, d_codes_right, int(H), int(W), int(code_pitch), int(min_disp), int(num_disp),
+            int(win), int(row0), int(row1), d_disp16, int(out_pitch), stream or None))
+
+    def census(self, gray: np.ndarray) -> np.ndarray:
+        """H x W uint64 census codes of a gray image (bit k: neighbour k of the 9 x 7
+        neighbourhood is darker than the centre)."""
+        gray, H, W, C = _image(gray)
+        if C != 1:
+            raise ValueError("census() expects a gray image")
+        d_g, d_c = self.dev_alloc(H * W), self.dev_alloc(8 * H * W)
+        try:
+            self.to_device(d_g, gray)
+            self.census_dev(d_g, H, W, W, 0, H, d_c, W)
+            return self.to_host(d_c, (H, W), np.uint64)
+        finally:
+            self.dev_free(d_g)
+            self.dev_free(d_c)
+
+    def census_match(self, codes_l: np.ndarray, codes_r: np.ndarray, min_disp: int, num_disp: int,
+                     win: int) -> np.ndarray:
+        """int16 x16 winner-take-all map of two H x W uint64 code planes (any 64-bit binary
+        descriptors): window sums of the Hamming distance, first argmin."""
+        cl = np.ascontiguousarray(codes_l, np.uint64)
+        cr = np.ascontiguousarray(codes_r, np.uint64)
+        if cl.ndim != 2 or cl.shape != cr.shape:
+            raise ValueError("census_match() expects two H x W uint64 planes of one shape")
+        H, W = cl.shape
+        d_l, d_r, d_o = self.dev_alloc(cl.nbytes), self.dev_alloc(cr.nbytes), self.dev_alloc(2 * H * W)
+        try:
+            self.to_device(d_l, cl)
+            self.to_device(d_r, cr)
+            self.census_match_dev(d_l, d_r, H, W, W, min_disp, num_disp, win, 0, H, d_o, W)
+            return self.to_host(d_o, (H, W), np.int16)
+        finally:
+            self.dev_free(d_l)
+            self.dev_free(d_r)
+            self.dev_free(d_o)
 
     # -- rectification (initUndistortRectifyMap / remap) ------------------------------------
     @staticmethod
